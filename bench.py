@@ -38,6 +38,17 @@ Input modes (--input-mode):
   local             each rank generates its own shard (no transfer at all).
 At N = 1 all three run the same forward.
 
+A plain run sets up, primes, warms up, times the --steps pipelined steps and
+prints the JSON line (the latency fields are null). ``--full`` adds the
+measurements that take runs of their own: the unpipelined per-batch latency
+(--latency-steps), the batch-1 GPU latency (--latency-queries), the query
+latency through a dmlc-node cluster (--e2e-queries), and the sanity check of
+the gathered answers. ``--dump-outputs DIR`` writes the answers of the last
+timed step (what the coordinator receives: every image's top-1 class and its
+probability) as DIR/top1_class.npy and DIR/top1_prob.npy, float32, in the
+order of the global batch; models, images and the step -> batch mapping are
+seeded, so two builds run with the same arguments can be compared.
+
 Reference numbers (CS425MP4Report.pdf p.2): ResNet18 mean query latency
 158.94 ms on CPU VMs, i.e. 6.29 images/s for one query stream; there is no
 published images/s figure, so ``vs_baseline`` divides by that derived rate.
@@ -129,11 +140,18 @@ def main():
     ap.add_argument("--prime-steps", type=int, default=40,
                     help="untimed pipeline steps at setup, before the --warmup steps (brings the GPU clocks up: "
                          "measured 267k img/s after 5 warmup steps alone vs 290k after 30, profiles/r2_warmup_ramp.txt)")
-    ap.add_argument("--latency-steps", type=int, default=50, help="unpipelined steps for the batch latency")
-    ap.add_argument("--latency-queries", type=int, default=200, help="batch-1 GPU queries (GPU-only latency)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: batch latency, batch-1 GPU latency, "
+                         "query latency through a dmlc-node cluster, and the check of the gathered answers")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's answers (top-1 class and probability of every image of the "
+                         "global batch) to DIR/top1_class.npy and DIR/top1_prob.npy (float32)")
+    ap.add_argument("--latency-steps", type=int, default=50, help="(--full) unpipelined steps for the batch latency")
+    ap.add_argument("--latency-queries", type=int, default=200,
+                    help="(--full) batch-1 GPU queries (GPU-only latency)")
     ap.add_argument("--profile-ops", action="store_true", help="print per-op times of one eager forward")
     ap.add_argument("--e2e-queries", type=int, default=200,
-                    help="queries through a dmlc-node cluster for the reference-definition query latency (0: skip)")
+                    help="(--full) queries through a dmlc-node cluster for the reference-definition query latency (0: skip)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: every rank a process with a host worker (a forward of B images takes "
                          "B x --dry-us-per-image of modelled time, + --dry-coord-extra-us on rank 0 for its send "
@@ -275,14 +293,27 @@ def main():
         per_rank_s = [float(x) for x in gathered]
         elapsed = max(per_rank_s)
 
+    full = args.full
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's gathered answers, in global-batch order
+        import numpy as np
+        idx, prob = runner.last_results()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "top1_class.npy"), np.asarray(idx, dtype=np.float32))
+        np.save(os.path.join(args.dump_outputs, "top1_prob.npy"), np.asarray(prob, dtype=np.float32))
+
     # Per-batch latency: unpipelined steps, scatter issue -> answers on the
     # coordinator's host.
-    lat = runner.run(pool_ptr, n_pool, args.warmup + args.steps, args.latency_steps, pipelined=False)
-    batch_lat = lat["step_ms"]
-    barrier()
+    n_lat = args.latency_steps if full else 0
+    batch_lat = []
+    if n_lat > 0:
+        lat = runner.run(pool_ptr, n_pool, args.warmup + args.steps, n_lat, pipelined=False)
+        batch_lat = lat["step_ms"]
+        barrier()
 
+    # (a dry run exists to check the path, so it always checks its answers)
     answers_checked = False
-    if rank == 0:
+    if rank == 0 and (full or dry):
         idx, prob = runner.last_results()
         assert len(idx) == sum(counts)
         assert min(idx) >= 0 and max(idx) < 1000, "bad class ids"
@@ -292,7 +323,7 @@ def main():
             # (csrc/comm/dp.h make_host_worker): the last step's gathered
             # answers must be those of the images that step was given
             G = sum(counts)
-            last = args.warmup + args.steps + args.latency_steps - 1
+            last = args.warmup + args.steps + n_lat - 1
             if scatter:
                 imgs = pool[:(n_pool // G) * G].view(-1, G, S, S, 3)[last % (n_pool // G)]
             else:
@@ -306,7 +337,7 @@ def main():
     # answer). Not the reference's query definition (which includes the RPC
     # and the JPEG decode): that one is tools/bench_jobs.py's.
     qlat = []
-    if rank == 0 and args.latency_queries > 0 and not dry:
+    if rank == 0 and full and args.latency_queries > 0 and not dry:
         q_eng = InferenceEngine(args.model, sd, device=local_rank, max_batch=1, options=opts)
         qimg = pool[:1].contiguous()
         qout = (torch.empty(1, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.float32, device=dev))
@@ -322,7 +353,7 @@ def main():
     # decode + resize + forward + top-1, one query at a time) through a
     # one-node dmlc-node cluster on this GPU.
     e2e = None
-    if rank == 0 and args.e2e_queries > 0 and not dry:
+    if rank == 0 and full and args.e2e_queries > 0 and not dry:
         try:
             from dmlc.serve.e2e import query_latency
             e2e = query_latency(args.e2e_queries, args.model if args.model in ("resnet18", "alexnet") else "resnet18",
@@ -394,6 +425,7 @@ def main():
             "gpu_batch1_latency_p95_ms": round(pct(qlat, 95), 4) if qlat else None,
             "tflops_effective": round(value * eng.gflop_per_image / 1e3, 1) if eng else None,
             "dry_run": dry,
+            "full": full,
         }
         if dry:
             res["answers_checked"] = answers_checked

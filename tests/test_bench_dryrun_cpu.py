@@ -23,7 +23,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHORT = ["--steps", "4", "--warmup", "2", "--prime-steps", "4", "--calib-steps", "4", "--latency-steps", "2"]
+SHORT = ["--full", "--steps", "4", "--warmup", "2", "--prime-steps", "4", "--calib-steps", "4", "--latency-steps", "2"]
 
 
 def _json_line(out: str) -> dict:

@@ -42,7 +42,7 @@ step() {  # name timeout cmd...
 }
 
 bench_short() {  # model: a short bench run whose dispatches are the model's b256 forward
-  echo python3 bench.py --model "$1" --steps 4 --warmup 2 --prime-steps 2 --latency-steps 6 \
+  echo python3 bench.py --full --model "$1" --steps 4 --warmup 2 --prime-steps 2 --latency-steps 6 \
     --latency-queries 0 --e2e-queries 0
 }
 
@@ -57,12 +57,12 @@ for s in "$@"; do
     bench200)
       step bench200 400 python bench.py --steps 200 --warmup 20 --latency-queries 0 --e2e-queries 0 ;;
     r50)
-      step r50 400 python bench.py --model resnet50_fp8 --steps 100 --warmup 20 --latency-queries 0 \
+      step r50 400 python bench.py --full --model resnet50_fp8 --steps 100 --warmup 20 --latency-queries 0 \
         --e2e-queries 0 --latency-steps 10 ;;
     trace:*)
       m=${s#trace:}
       step "trace_$m" 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$m" -o run \
-        -- python3 bench.py --model "$m" --steps 20 --warmup 5 --prime-steps 5 --latency-queries 0 \
+        -- python3 bench.py --full --model "$m" --steps 20 --warmup 5 --prime-steps 5 --latency-queries 0 \
         --e2e-queries 0 --latency-steps 50
       python tools/lane_stats.py "$OUT/trace_$m/run_kernel_trace.csv" --lat 50 > "$OUT/lane_stats_$m.txt" 2>&1
       head -30 "$OUT/lane_stats_$m.txt" ;;
