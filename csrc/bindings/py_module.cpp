@@ -14,6 +14,7 @@
 #include "../kernels/kernels.h"
 #include "../runtime/engine.h"
 #include "../runtime/jpeg.h"
+#include "../runtime/jpeg_gpu.h"
 #include "../runtime/ot_io.h"
 
 namespace py = pybind11;
@@ -50,6 +51,68 @@ py::dict from_weight_map(const WeightMap& w) {
     d[py::str(kv.first)] = a;
   }
   return d;
+}
+
+// JpegLayout <-> {"width", "height", "ncomp", "hmax", "vmax", "comps": [{"h", "v", "bw", "bh", "offset", "qt"}]}
+py::dict layout_to_dict(const JpegLayout& l) {
+  py::dict d;
+  d["width"] = l.width;
+  d["height"] = l.height;
+  d["ncomp"] = l.ncomp;
+  d["hmax"] = l.hmax;
+  d["vmax"] = l.vmax;
+  py::list comps;
+  for (int i = 0; i < l.ncomp; ++i) {
+    py::dict c;
+    c["h"] = l.comp[i].h;
+    c["v"] = l.comp[i].v;
+    c["bw"] = l.comp[i].bw;
+    c["bh"] = l.comp[i].bh;
+    c["offset"] = l.comp[i].offset;
+    py::array_t<uint16_t> q(64);
+    std::copy(l.comp[i].qt, l.comp[i].qt + 64, q.mutable_data());
+    c["qt"] = q;
+    comps.append(c);
+  }
+  d["comps"] = comps;
+  return d;
+}
+
+JpegLayout layout_from_dict(const py::dict& d) {
+  JpegLayout l;
+  l.width = py::cast<int>(d["width"]);
+  l.height = py::cast<int>(d["height"]);
+  l.hmax = py::cast<int>(d["hmax"]);
+  l.vmax = py::cast<int>(d["vmax"]);
+  const py::list comps = d["comps"];
+  if (comps.size() < 1 || comps.size() > 3) throw std::invalid_argument("jpeg layout: 1 to 3 components");
+  l.ncomp = (int)comps.size();
+  if (d.contains("ncomp") && py::cast<int>(d["ncomp"]) != l.ncomp) throw std::invalid_argument("jpeg layout: ncomp");
+  size_t off = 0;
+  for (int i = 0; i < l.ncomp; ++i) {
+    const py::dict c = comps[i];
+    JpegComp& lc = l.comp[i];
+    lc.h = py::cast<int>(c["h"]);
+    lc.v = py::cast<int>(c["v"]);
+    lc.bw = c.contains("bw") ? py::cast<int>(c["bw"]) : 0;
+    lc.bh = c.contains("bh") ? py::cast<int>(c["bh"]) : 0;
+    if (lc.bw < 0 || lc.bh < 0 || lc.bw > 4096 || lc.bh > 4096) throw std::invalid_argument("jpeg layout: block counts");
+    lc.offset = c.contains("offset") ? py::cast<size_t>(c["offset"]) : off;
+    off = lc.offset + (size_t)lc.bw * lc.bh * 64;
+    if (c.contains("qt")) {
+      auto q = py::array_t<uint16_t, py::array::c_style | py::array::forcecast>::ensure(c["qt"]);
+      if (!q || q.size() != 64) throw std::invalid_argument("jpeg layout: qt must hold 64 values");
+      std::copy(q.data(), q.data() + 64, lc.qt);
+    }
+  }
+  return l;
+}
+
+// a host copy of device descriptors, as jpeg_gpu_plan returned it
+const JpegGpuImage* host_descs(const py::array_t<uint8_t, py::array::c_style>& a, int* n) {
+  if (a.size() % (py::ssize_t)sizeof(JpegGpuImage)) throw std::invalid_argument("jpeg descriptors: bad size");
+  *n = (int)(a.size() / (py::ssize_t)sizeof(JpegGpuImage));
+  return reinterpret_cast<const JpegGpuImage*>(a.data());
 }
 
 }  // namespace
@@ -346,6 +409,84 @@ PYBIND11_MODULE(_C, m) {
     std::copy(img.rgb.begin(), img.rgb.end(), a.mutable_data());
     return a;
   });
+  // split decode: entropy decoding on the host -> (layout, int16 coefficients)
+  m.def("decode_jpeg_coeffs", [](py::bytes data) {
+    std::string s = data;
+    std::vector<int16_t> buf;
+    JpegLayout l;
+    {
+      py::gil_scoped_release nogil;
+      l = decode_jpeg_coeffs((const uint8_t*)s.data(), s.size(), [&](size_t n) {
+        buf.resize(n);
+        return buf.data();
+      });
+    }
+    py::array_t<int16_t> a((py::ssize_t)buf.size());
+    std::copy(buf.begin(), buf.end(), a.mutable_data());
+    return py::make_tuple(layout_to_dict(l), a);
+  });
+  m.def("jpeg_gpu_supported", [](const py::dict& layout) { return jpeg_gpu_supported(layout_from_dict(layout)); });
+  // the decoder's colour stage on caller-supplied planes (u8 [8 bh][8 bw] each) -> [height][width][3]
+  m.def("ycc_planes_to_rgb", [](const std::vector<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>>& planes,
+                                const py::dict& layout) {
+    const JpegLayout l = layout_from_dict(layout);
+    if (!jpeg_gpu_supported(l)) throw std::invalid_argument("ycc_planes_to_rgb: unsupported layout");
+    if ((int)planes.size() != l.ncomp) throw std::invalid_argument("ycc_planes_to_rgb: one plane per component");
+    const uint8_t* ptr[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < l.ncomp; ++i) {
+      const JpegComp& c = l.comp[i];
+      const int cw = (l.width * c.h + l.hmax - 1) / l.hmax, ch = (l.height * c.v + l.vmax - 1) / l.vmax;
+      if (planes[i].ndim() != 2 || planes[i].shape(0) != 8 * c.bh || planes[i].shape(1) != 8 * c.bw)
+        throw std::invalid_argument("ycc_planes_to_rgb: plane " + std::to_string(i) + " is not [8 bh][8 bw]");
+      if (cw > 8 * c.bw || ch > 8 * c.bh) throw std::invalid_argument("ycc_planes_to_rgb: plane smaller than the image");
+      ptr[i] = planes[i].data();
+    }
+    py::array_t<uint8_t> out({l.height, l.width, 3});
+    ycc_planes_to_rgb(ptr, l, out.mutable_data());
+    return out;
+  });
+  // device descriptors for a batch whose coefficients and planes lie back to
+  // back in image order: (descriptors as bytes, tables float32 [T][64],
+  // coefficient count, plane bytes)
+  m.def("jpeg_gpu_plan", [](const std::vector<py::dict>& layouts, const std::vector<uintptr_t>& rgb) {
+    if (layouts.size() != rgb.size()) throw std::invalid_argument("jpeg_gpu_plan: one destination per image");
+    py::array_t<uint8_t> descs((py::ssize_t)(layouts.size() * sizeof(JpegGpuImage)));
+    auto* d = reinterpret_cast<JpegGpuImage*>(descs.mutable_data());
+    std::vector<float> tables;
+    size_t coef = 0, plane = 0;
+    for (size_t i = 0; i < layouts.size(); ++i) {
+      JpegLayout l = layout_from_dict(layouts[i]);
+      size_t off = 0;  // components back to back, whatever the dict's offsets say
+      for (int c = 0; c < l.ncomp; ++c) {
+        l.comp[c].offset = off;
+        off += (size_t)l.comp[c].bw * l.comp[c].bh * 64;
+      }
+      const int t0 = (int)(tables.size() / 64);
+      d[i] = jpeg_gpu_image(l, P<uint8_t>(rgb[i]), coef, plane, t0);
+      tables.resize(tables.size() + 64 * (size_t)l.ncomp);
+      jpeg_gpu_tables(l, tables.data() + 64 * (size_t)t0);
+      coef += l.total();
+      plane += jpeg_plane_bytes(l);
+    }
+    py::array_t<float> t({(py::ssize_t)(tables.size() / 64), (py::ssize_t)64});
+    std::copy(tables.begin(), tables.end(), t.mutable_data());
+    return py::make_tuple(descs, t, coef, plane);
+  });
+  m.def("jpeg_idct_planes", [](const py::array_t<uint8_t, py::array::c_style>& descs, uintptr_t dev, uintptr_t qf,
+                               int n_tables, uintptr_t coef, size_t coef_elems, uintptr_t planes, size_t plane_bytes,
+                               uintptr_t stream) {
+    int n = 0;
+    const JpegGpuImage* h = host_descs(descs, &n);
+    jpeg_idct_planes(h, P<JpegGpuImage>(dev), n, P<float>(qf), n_tables, P<int16_t>(coef), coef_elems,
+                     P<uint8_t>(planes), plane_bytes, S(stream));
+  }, py::arg("descs"), py::arg("dev"), py::arg("qf"), py::arg("n_tables"), py::arg("coef"), py::arg("coef_elems"),
+        py::arg("planes"), py::arg("plane_bytes"), py::arg("stream"));
+  m.def("jpeg_planes_to_rgb", [](const py::array_t<uint8_t, py::array::c_style>& descs, uintptr_t dev, uintptr_t planes,
+                                 size_t plane_bytes, uintptr_t stream) {
+    int n = 0;
+    const JpegGpuImage* h = host_descs(descs, &n);
+    jpeg_planes_to_rgb(h, P<JpegGpuImage>(dev), n, P<uint8_t>(planes), plane_bytes, S(stream));
+  }, py::arg("descs"), py::arg("dev"), py::arg("planes"), py::arg("plane_bytes"), py::arg("stream"));
 
   // ---------------------------------------------------------------- .ot
   m.def("ot_load", [](const std::string& path) { return from_weight_map(ot_load(path)); });

@@ -133,7 +133,28 @@ int main(int argc, char** argv) {
     try {
       if (which < 6 && !jpegs.empty()) {
         const std::string in = mutate(jpegs[rng() % jpegs.size()], rng);
-        Image img = decode_jpeg((const uint8_t*)in.data(), in.size());
+        // the coefficient parser first: it must agree with decode_jpeg on
+        // accept / reject, and on the size when both accept
+        std::vector<int16_t> coef;
+        JpegLayout lay;
+        bool coef_ok = true;
+        try {
+          lay = decode_jpeg_coeffs((const uint8_t*)in.data(), in.size(), [&](size_t n) {
+            coef.resize(n);
+            return coef.data();
+          });
+          if (lay.total() != coef.size()) std::abort();
+        } catch (const std::exception&) {
+          coef_ok = false;
+        }
+        Image img;
+        try {
+          img = decode_jpeg((const uint8_t*)in.data(), in.size());
+        } catch (const std::exception&) {
+          if (coef_ok) std::abort();
+          throw;
+        }
+        if (!coef_ok || lay.width != img.width || lay.height != img.height) std::abort();
         if ((size_t)img.width * img.height * 3 != img.rgb.size()) std::abort();
       } else if (which < 8) {
         const std::string in = mutate(msgs[rng() % msgs.size()], rng);

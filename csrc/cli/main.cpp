@@ -363,6 +363,7 @@ void handle_line(Node& n, const std::string& line) {
                  std::to_string(cs.staged) + " evictions " + std::to_string(cs.evictions) + " entries " +
                  std::to_string(cs.entries) + " bytes " + std::to_string(cs.bytes) + " capacity " +
                  std::to_string(cs.capacity) + " prefetched " + std::to_string(n.member->prefetched()));
+        out_line("jpeg gpu " + std::to_string(cs.jpeg_gpu) + " cpu " + std::to_string(cs.jpeg_cpu));
       }
     } else if (c == "prefetch") {
       // stage the dataset's query images into the executor's (HBM) cache
@@ -420,7 +421,7 @@ int run_node(const Args& a) {
     }
     ex = make_executor(a.get("executor", "auto"), devs, a.geti("max-batch", 256),
                        (size_t)a.geti("hbm-cache-mb", 4096) << 20, a.geti("min-shard", 32), a.geti("lanes", 2),
-                       a.geti("batch-window-us", 200));
+                       a.geti("batch-window-us", 200), a.has("jpeg-gpu"));
     if (ex) {
       // the GPUs are split between the jobs in this order (first floor(n/2)
       // to the first job, src/services.rs:199-211)
@@ -500,15 +501,22 @@ int run_node(const Args& a) {
 
 int run_classify(const Args& a) {
   const std::string model = a.get("model", "alexnet");
+  const std::vector<std::string> paths = split(a.get("image"), ',');
+  // --jpeg-gpu: the executor reads the files itself and finishes their decode on the GPU
+  const bool jpeg_gpu = a.has("jpeg-gpu");
   std::vector<Image> imgs;
-  for (const auto& p : split(a.get("image"), ',')) imgs.push_back(decode_jpeg_file(p));
+  if (!jpeg_gpu)
+    for (const auto& p : paths) imgs.push_back(decode_jpeg_file(p));
   // all images in one batch (one forward on the GPU executor)
-  auto ex = make_executor(a.get("executor", "cpu"), a.geti("device", 0), std::max<int>(1, (int)imgs.size()));
+  const int max_batch = std::max<int>(1, (int)paths.size());
+  auto ex = jpeg_gpu ? make_executor(a.get("executor", "cpu"), std::vector<int>{a.geti("device", 0)}, max_batch,
+                                     (size_t)4 << 30, 32, 2, 200, true)
+                     : make_executor(a.get("executor", "cpu"), a.geti("device", 0), max_batch);
   if (!ex) throw std::runtime_error("no inference executor in this build");
   ex->load_model(model, a.get("weights"));
   const Labels labels = Labels::load(a.get("labels", "synset_words.txt"));
   const int64_t t0 = steady_us();
-  const auto preds = ex->predict(model, imgs);
+  const auto preds = jpeg_gpu ? ex->predict_files(model, paths) : ex->predict(model, imgs);
   const int64_t dt = steady_us() - t0;
   for (size_t i = 0; i < preds.size(); ++i) {
     char buf[64];
@@ -535,8 +543,10 @@ int main(int argc, char** argv) {
                  "                 [--max-attempts 3] [--watch-ms 250] [--query-timeout-ms 120000]\n"
                  "                 [--query-timeout-min-ms 1000]\n"
                  "                 [--max-batch 256] [--batch-window-us 200] [--hbm-cache-mb 4096] [--prefetch]\n"
+                 "                 [--jpeg-gpu]\n"
                  "       dmlc-node selftest\n"
-                 "       dmlc-node classify --model M --weights W.ot --labels L --image I.JPEG [--executor cpu|gpu]\n";
+                 "       dmlc-node classify --model M --weights W.ot --labels L --image I.JPEG [--executor cpu|gpu]\n"
+                 "                      [--jpeg-gpu]\n";
     return 0;
   }
   return run_node(parse(argc, argv, 1));

@@ -156,6 +156,36 @@ struct ImageDesc {
 };
 void resize_u8_ragged(const ImageDesc* descs, uint8_t* out, int B, int S, hipStream_t s);
 
+// The GPU half of the split JPEG decode (jpeg_finish.hip) over a ragged batch:
+// entropy-decoded coefficients (decode_jpeg_coeffs) -> RGB u8 HWC. Image i =
+// descs[i]; component c of it has bw[c] x bh[c] blocks, int16 coefficients
+// [bh][bw][64] (natural order) at coef + coef_off[c], its dequantisation table
+// (jpeg_aan_table: 64 floats) at qf + 64 * qt[c], and its u8 plane
+// [8 bh][8 bw] at planes + plane_off[c]; chroma is subsampled by hf / vf (1 or
+// 2) against luma (component 0: 1, 1). csrc/runtime/jpeg_gpu.h fills one from
+// a JpegLayout.
+struct JpegGpuImage {
+  uint8_t* rgb;  // destination, width * height * 3 bytes, 4-byte aligned
+  int width, height, ncomp;
+  int hf[3], vf[3];
+  int bw[3], bh[3];
+  int qt[3];
+  long long coef_off[3];   // int16 units, multiple of 8
+  long long plane_off[3];  // bytes, multiple of 8
+};
+// `host` is the caller's copy of the descriptors at `dev` (device memory,
+// uploaded on the same stream before the call): every geometry is checked on
+// it against coef_elems / n_tables / plane_bytes, and the grid is sized from
+// it. Stage 1: dequantise + AAN inverse DCT (fp32) + 128, round half up,
+// clamp -> planes (qf, coef 16-byte aligned; planes 8-byte aligned).
+void jpeg_idct_planes(const JpegGpuImage* host, const JpegGpuImage* dev, int n, const float* qf, int n_tables,
+                      const int16_t* coef, size_t coef_elems, uint8_t* planes, size_t plane_bytes, hipStream_t s);
+// Stage 2: centred 3:1 triangle chroma upsampling + 16.16 fixed-point YCbCr ->
+// RGB into descs[i].rgb, bit-identical to the host's ycc_planes_to_rgb
+// (grayscale replicates Y).
+void jpeg_planes_to_rgb(const JpegGpuImage* host, const JpegGpuImage* dev, int n, const uint8_t* planes,
+                        size_t plane_bytes, hipStream_t s);
+
 // Fused ResNet stem: conv 7x7/s2/p3 (folded BN) + ReLU + maxpool 3x3/s2/p1.
 //   x : paired image [B, S+6, Wq, 8] bf16 (preprocess_u8 pad=3, paired)
 //   w : bf16 [64, 224], k = kh*32 + q*8 + e: chunk q covers kw = 2q, 2q+1,

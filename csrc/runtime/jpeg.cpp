@@ -85,6 +85,7 @@ struct Comp {
   int td = 0, ta = 0;
   int bw = 0, bh = 0;  // blocks per line / column in the plane
   std::vector<uint8_t> plane;  // bw*8 x bh*8
+  size_t coff = 0;  // coefficient output: the component's offset (int16 units)
   int pred = 0;
 };
 
@@ -408,7 +409,13 @@ void ycc_row(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint8_t* o,
 // rounded. Same positions as the generic bilinear path ((x+0.5)/f - 0.5,
 // clamped to the plane's valid area). The interior loops are branch-free
 // (the edge samples are handled apart) so the compiler vectorises them.
-void chroma_row(const Comp& c, int hf, int vf, int y, int W, int H, int hmax, int vmax, uint8_t* out,
+// A component's plane as the colour stage reads it.
+struct PlaneRef {
+  const uint8_t* p;
+  int h, v, bw;
+};
+
+void chroma_row(const PlaneRef& c, int hf, int vf, int y, int W, int H, int hmax, int vmax, uint8_t* out,
                 std::vector<uint16_t>& tmp) {
   const int pw = c.bw * 8;
   const int cw = (W * c.h + hmax - 1) / hmax, ch = (H * c.v + vmax - 1) / vmax;
@@ -429,8 +436,8 @@ void chroma_row(const Comp& c, int hf, int vf, int y, int W, int H, int hmax, in
     wa = 3;
     wb = 1;
   }
-  const uint8_t* r0 = c.plane.data() + (size_t)y0 * pw;
-  const uint8_t* r1 = c.plane.data() + (size_t)y1 * pw;
+  const uint8_t* r0 = c.p + (size_t)y0 * pw;
+  const uint8_t* r1 = c.p + (size_t)y1 * pw;
   tmp.resize((size_t)cw);
   uint16_t* t = tmp.data();
   for (int x = 0; x < cw; ++x) t[x] = (uint16_t)(wa * r0[x] + wb * r1[x]);  // x4
@@ -467,13 +474,13 @@ void chroma_row(const Comp& c, int hf, int vf, int y, int W, int H, int hmax, in
 // Fast colour conversion for 1 or 3 components with chroma subsampled by 1
 // or 2 per axis (4:4:4, 4:2:2, 4:2:0, 4:4:0 — essentially every JPEG);
 // false for other layouts (the generic float path handles them).
-bool convert_fast(const std::vector<Comp>& comps, int hmax, int vmax, int W, int H, uint8_t* rgb) {
-  const Comp& Yc = comps[0];
+bool convert_fast(const PlaneRef* comps, int nc, int hmax, int vmax, int W, int H, uint8_t* rgb) {
+  const PlaneRef& Yc = comps[0];
   if (Yc.h != hmax || Yc.v != vmax) return false;
   const int pw = Yc.bw * 8;
-  if (comps.size() == 1) {
+  if (nc == 1) {
     for (int y = 0; y < H; ++y) {
-      const uint8_t* yr = Yc.plane.data() + (size_t)y * pw;
+      const uint8_t* yr = Yc.p + (size_t)y * pw;
       uint8_t* o = rgb + (size_t)y * W * 3;
       for (int x = 0; x < W; ++x) o[3 * x] = o[3 * x + 1] = o[3 * x + 2] = yr[x];
     }
@@ -481,7 +488,7 @@ bool convert_fast(const std::vector<Comp>& comps, int hmax, int vmax, int W, int
   }
   int hf[2], vf[2];
   for (int k = 0; k < 2; ++k) {
-    const Comp& c = comps[k + 1];
+    const PlaneRef& c = comps[k + 1];
     if (hmax % c.h || vmax % c.v) return false;
     hf[k] = hmax / c.h;
     vf[k] = vmax / c.v;
@@ -490,8 +497,8 @@ bool convert_fast(const std::vector<Comp>& comps, int hmax, int vmax, int W, int
   if (hf[0] == 1 && vf[0] == 1 && hf[1] == 1 && vf[1] == 1) {  // 4:4:4: planes read in place
     const int cpw = comps[1].bw * 8, rpw = comps[2].bw * 8;
     for (int y = 0; y < H; ++y)
-      ycc_row(Yc.plane.data() + (size_t)y * pw, comps[1].plane.data() + (size_t)y * cpw,
-              comps[2].plane.data() + (size_t)y * rpw, rgb + (size_t)y * W * 3, W);
+      ycc_row(Yc.p + (size_t)y * pw, comps[1].p + (size_t)y * cpw,
+              comps[2].p + (size_t)y * rpw, rgb + (size_t)y * W * 3, W);
     return true;
   }
   std::vector<uint8_t> cb((size_t)W), cr((size_t)W);
@@ -499,15 +506,22 @@ bool convert_fast(const std::vector<Comp>& comps, int hmax, int vmax, int W, int
   for (int y = 0; y < H; ++y) {
     chroma_row(comps[1], hf[0], vf[0], y, W, H, hmax, vmax, cb.data(), tmp);
     chroma_row(comps[2], hf[1], vf[1], y, W, H, hmax, vmax, cr.data(), tmp);
-    ycc_row(Yc.plane.data() + (size_t)y * pw, cb.data(), cr.data(), rgb + (size_t)y * W * 3, W);
+    ycc_row(Yc.p + (size_t)y * pw, cb.data(), cr.data(), rgb + (size_t)y * W * 3, W);
   }
   return true;
 }
 
 }  // namespace
 
-// Decodes into the buffer out(W, H) returns (W * H * 3 bytes).
-static void decode_jpeg_impl(const uint8_t* data, size_t size, const std::function<uint8_t*(int, int)>& out) {
+// kCoef = false: decodes into the buffer out(W, H) returns (W * H * 3 bytes).
+// kCoef = true: the same walk over markers, tables, scans and restart
+// intervals, but a decoded block is stored as quantised int16 coefficients in
+// the buffer alloc returns (no dequantisation, IDCT or colour conversion);
+// fills *lay.
+template <bool kCoef>
+static void decode_jpeg_impl(const uint8_t* data, size_t size, const std::function<uint8_t*(int, int)>& out,
+                             const std::function<int16_t*(size_t)>* alloc = nullptr, JpegLayout* lay = nullptr) {
+  int16_t* coef = nullptr;
   const uint8_t* p = data;
   const uint8_t* end = data + size;
   if (size < 4 || p[0] != 0xFF || p[1] != 0xD8) throw std::runtime_error("jpeg: missing SOI");
@@ -589,7 +603,26 @@ static void decode_jpeg_impl(const uint8_t* data, size_t size, const std::functi
         for (auto& c : comps) {
           c.bw = mcux * c.h;
           c.bh = mcuy * c.v;
-          c.plane.assign((size_t)c.bw * 8 * c.bh * 8, 0);
+          if (!kCoef) c.plane.assign((size_t)c.bw * 8 * c.bh * 8, 0);
+        }
+        if (kCoef) {
+          lay->width = W;
+          lay->height = H;
+          lay->ncomp = nc;
+          lay->hmax = hmax;
+          lay->vmax = vmax;
+          size_t off = 0;
+          for (int i = 0; i < nc; ++i) {
+            JpegComp& lc = lay->comp[i];
+            lc.h = comps[i].h;
+            lc.v = comps[i].v;
+            lc.bw = comps[i].bw;
+            lc.bh = comps[i].bh;
+            lc.offset = comps[i].coff = off;
+            off += (size_t)lc.bw * lc.bh * 64;
+          }
+          coef = (*alloc)(off);
+          std::memset(coef, 0, off * sizeof(int16_t));
         }
         frame = true;
         break;
@@ -625,6 +658,9 @@ static void decode_jpeg_impl(const uint8_t* data, size_t size, const std::functi
             throw std::runtime_error("jpeg: missing huffman table");
           sc.push_back(c);
         }
+        if (kCoef)  // the tables this scan's blocks are dequantised with, natural order
+          for (auto* c : sc)
+            for (int k = 0; k < 64; ++k) lay->comp[c - comps.data()].qt[kZigzag[k]] = qt[c->tq][k];
         BitReader br(seg_end, end);
         float blk[64];
         // dequantisation folded with the AAN scale factors, natural order
@@ -632,13 +668,27 @@ static void decode_jpeg_impl(const uint8_t* data, size_t size, const std::functi
         for (int t = 0; t < 4; ++t)
           for (int k = 0; k < 64; ++k) qf[t][kZigzag[k]] = qt[t][k] * kAan.f[kZigzag[k]];
         int mcus_left = restart;
-        auto decode_block = [&](Comp& c, uint8_t* dst, int stride) {
-          std::memset(blk, 0, sizeof(blk));
+        // One block's symbols -> the float block (dequantised, then IDCT into
+        // the plane at pixel block (bx, by)) or the int16 block of the
+        // coefficient buffer.
+        auto decode_block = [&](Comp& c, int bx, int by) {
           const float* q = qf[c.tq];
+          int16_t* cb = nullptr;
+          if (kCoef) {
+            cb = coef + c.coff + ((size_t)by * c.bw + bx) * 64;
+            std::memset(cb, 0, 64 * sizeof(int16_t));  // (a later scan may decode the block again)
+          } else {
+            std::memset(blk, 0, sizeof(blk));
+          }
+          auto put = [&](int z, int v) {
+            if (kCoef) cb[z] = (int16_t)v;
+            else blk[z] = (float)v * q[z];
+          };
           const int t = decode_huff(dc[c.td], br);
           if (t > 15) throw std::runtime_error("jpeg: bad DC magnitude");
           c.pred += t ? extend(br.bits(t), t) : 0;
-          blk[0] = (float)c.pred * q[0];
+          if (kCoef) cb[0] = (int16_t)std::min(std::max(c.pred, -32768), 32767);
+          else blk[0] = (float)c.pred * q[0];
           const Huff& ha = ac[c.ta];
           for (int k = 1; k < 64;) {
             const int32_t fe = ha.fast[br.peek(Huff::kFastBits)];
@@ -646,8 +696,7 @@ static void decode_jpeg_impl(const uint8_t* data, size_t size, const std::functi
               br.skip(fe & 31);
               k += (fe >> 5) & 15;
               if (k > 63) break;
-              const int z = kZigzag[k];
-              blk[z] = (float)(fe >> 16) * q[z];
+              put(kZigzag[k], fe >> 16);
               ++k;
               continue;
             }
@@ -660,11 +709,10 @@ static void decode_jpeg_impl(const uint8_t* data, size_t size, const std::functi
             }
             k += r;
             if (k > 63) break;
-            const int z = kZigzag[k];
-            blk[z] = (float)extend(br.bits(s), s) * q[z];
+            put(kZigzag[k], extend(br.bits(s), s));
             ++k;
           }
-          idct8x8(blk, dst, stride);
+          if (!kCoef) idct8x8(blk, c.plane.data() + (size_t)by * 8 * c.bw * 8 + bx * 8, c.bw * 8);
         };
         auto handle_restart = [&]() {
           if (!restart) return;
@@ -686,7 +734,7 @@ static void decode_jpeg_impl(const uint8_t* data, size_t size, const std::functi
           for (int by = 0; by < nby; ++by)
             for (int bx = 0; bx < nbx; ++bx) {
               handle_restart();
-              decode_block(c, c.plane.data() + (size_t)by * 8 * c.bw * 8 + bx * 8, c.bw * 8);
+              decode_block(c, bx, by);
             }
         } else {
           const int mcux = (W + 8 * hmax - 1) / (8 * hmax), mcuy = (H + 8 * vmax - 1) / (8 * vmax);
@@ -698,7 +746,7 @@ static void decode_jpeg_impl(const uint8_t* data, size_t size, const std::functi
                 for (int v = 0; v < c.v; ++v)
                   for (int h = 0; h < c.h; ++h) {
                     const int bx = mx * c.h + h, by = my * c.v + v;
-                    decode_block(c, c.plane.data() + (size_t)by * 8 * c.bw * 8 + bx * 8, c.bw * 8);
+                    decode_block(c, bx, by);
                   }
               }
             }
@@ -716,9 +764,12 @@ static void decode_jpeg_impl(const uint8_t* data, size_t size, const std::functi
     p = seg_end;
   }
   if (!frame || !scanned) throw std::runtime_error("jpeg: no image data");
+  if (kCoef) return;
 
   uint8_t* rgb = out(W, H);
-  if (convert_fast(comps, hmax, vmax, W, H, rgb)) return;
+  PlaneRef refs[3];
+  for (size_t i = 0; i < comps.size(); ++i) refs[i] = PlaneRef{comps[i].plane.data(), comps[i].h, comps[i].v, comps[i].bw};
+  if (convert_fast(refs, (int)comps.size(), hmax, vmax, W, H, rgb)) return;
   auto sample = [&](const Comp& c, int x, int y) -> float {
     const int pw = c.bw * 8;
     if (c.h == hmax && c.v == vmax) return c.plane[(size_t)y * pw + x];
@@ -752,7 +803,7 @@ static void decode_jpeg_impl(const uint8_t* data, size_t size, const std::functi
 
 Image decode_jpeg(const uint8_t* data, size_t size) {
   Image img;
-  decode_jpeg_impl(data, size, [&](int w, int h) {
+  decode_jpeg_impl<false>(data, size, [&](int w, int h) {
     img.width = w;
     img.height = h;
     img.rgb.resize((size_t)w * h * 3);
@@ -762,7 +813,36 @@ Image decode_jpeg(const uint8_t* data, size_t size) {
 }
 
 void decode_jpeg_into(const uint8_t* data, size_t size, const std::function<uint8_t*(int, int)>& out) {
-  decode_jpeg_impl(data, size, out);
+  decode_jpeg_impl<false>(data, size, out);
+}
+
+JpegLayout decode_jpeg_coeffs(const uint8_t* data, size_t size, const std::function<int16_t*(size_t)>& alloc) {
+  JpegLayout lay;
+  decode_jpeg_impl<true>(data, size, nullptr, &alloc, &lay);
+  return lay;
+}
+
+bool jpeg_gpu_supported(const JpegLayout& l) {
+  if (l.ncomp != 1 && l.ncomp != 3) return false;
+  if (l.width <= 0 || l.height <= 0 || l.hmax < 1 || l.vmax < 1) return false;
+  if (l.comp[0].h != l.hmax || l.comp[0].v != l.vmax) return false;
+  for (int i = 1; i < l.ncomp; ++i) {
+    const JpegComp& c = l.comp[i];
+    if (c.h < 1 || c.v < 1 || l.hmax % c.h || l.vmax % c.v) return false;
+    if (l.hmax / c.h > 2 || l.vmax / c.v > 2) return false;
+  }
+  return true;
+}
+
+bool ycc_planes_to_rgb(const uint8_t* const* planes, const JpegLayout& l, uint8_t* rgb) {
+  if (!jpeg_gpu_supported(l)) return false;
+  PlaneRef refs[3];
+  for (int i = 0; i < l.ncomp; ++i) refs[i] = PlaneRef{planes[i], l.comp[i].h, l.comp[i].v, l.comp[i].bw};
+  return convert_fast(refs, l.ncomp, l.hmax, l.vmax, l.width, l.height, rgb);
+}
+
+void jpeg_aan_table(const uint16_t* qt, float* out) {
+  for (int z = 0; z < 64; ++z) out[z] = qt[z] * kAan.f[z];
 }
 
 Image decode_jpeg_file(const std::string& path) {

@@ -13,6 +13,7 @@
 #include <thread>
 
 #include "../runtime/engine.h"
+#include "../runtime/jpeg_gpu.h"
 #include "../runtime/ot_io.h"
 #include "../runtime/trace.h"
 #include "../comm/dp.h"
@@ -208,9 +209,10 @@ class CpuExecutor : public Executor {
 //     into the lane's batch buffer, no host or xGMI traffic).
 class GpuExecutor : public Executor {
  public:
-  GpuExecutor(std::vector<int> devices, int max_batch, size_t cache_bytes, int min_shard, int lanes, int batch_window_us)
+  GpuExecutor(std::vector<int> devices, int max_batch, size_t cache_bytes, int min_shard, int lanes, int batch_window_us,
+              bool jpeg_gpu)
       : devices_(std::move(devices)), max_batch_(max_batch), lanes_(std::max(1, std::min(lanes, 4))),
-        cache_cap_(cache_bytes) {
+        jpeg_gpu_(jpeg_gpu), cache_cap_(cache_bytes) {
     if (devices_.empty()) throw std::invalid_argument("GpuExecutor: no devices");
     kernel_stagger_for_lanes(lanes_);  // (one lane: the stream convs staggered, stagger.hip)
     for (int d : devices_) cache_bytes_dev_[d] = 0;
@@ -505,12 +507,40 @@ class GpuExecutor : public Executor {
   static constexpr int kS = 224;
   static constexpr size_t kDecodeThreads = 8;
   static constexpr int kStagers = 16;  // held through a miss's decode (it decodes into the pinned buffer)
+  // split JPEG decode: offsets in the staging buffer of the three tables and
+  // of the coefficients (the descriptor is at 0)
+  static constexpr size_t kJpegTables = 256, kJpegHeader = 1024;
+  static_assert(sizeof(JpegGpuImage) <= kJpegTables && kJpegTables + 3 * 64 * sizeof(float) <= kJpegHeader, "header");
 
   // A pinned bounce buffer pair and one side stream per GPU it has uploaded to.
   struct Stager {
     void* pinned[2] = {nullptr, nullptr};
     size_t pinned_bytes = 0;
     std::map<int, hipStream_t> streams;
+    // split JPEG decode, per GPU: the uploaded header + coefficients and the
+    // component planes between the two kernels; grown on demand
+    struct JpegScratch {
+      void* in = nullptr;
+      void* planes = nullptr;
+      size_t in_bytes = 0, plane_bytes = 0;
+    };
+    std::map<int, JpegScratch> jpeg;
+    // (the caller has made `device` current and nothing of this stager is in flight)
+    JpegScratch& jpeg_scratch(int device, size_t in_bytes, size_t plane_bytes) {
+      JpegScratch& j = jpeg[device];
+      auto grow = [](void*& p, size_t& have, size_t want) {
+        if (have >= want) return;
+        if (p) DMLC_HIP_CHECK(hipFree(p));
+        p = nullptr;
+        have = 0;
+        want = std::max<size_t>(want + want / 2, (size_t)1 << 20);
+        DMLC_HIP_CHECK(hipMalloc(&p, want));
+        have = want;
+      };
+      grow(j.in, j.in_bytes, in_bytes);
+      grow(j.planes, j.plane_bytes, plane_bytes);
+      return j;
+    }
     void ensure_pinned(size_t bytes) {
       if (pinned_bytes >= bytes) return;
       for (auto& p : pinned) {
@@ -535,6 +565,11 @@ class GpuExecutor : public Executor {
         (void)hipSetDevice(kv.first);
         (void)hipStreamSynchronize(kv.second);
         (void)hipStreamDestroy(kv.second);
+      }
+      for (auto& kv : jpeg) {
+        (void)hipSetDevice(kv.first);
+        if (kv.second.in) (void)hipFree(kv.second.in);
+        if (kv.second.planes) (void)hipFree(kv.second.planes);
       }
       for (auto p : pinned)
         if (p) (void)hipHostFree(p);
@@ -900,20 +935,53 @@ class GpuExecutor : public Executor {
     void* dev = nullptr;
     int img_h = 0, img_w = 0;
     size_t bytes = 0;
+    bool on_gpu = false;
     try {
-      decode_jpeg_into(jpeg.data(), jpeg.size(), [&](int w, int h) {
-        img_w = w;
-        img_h = h;
-        bytes = (size_t)w * h * 3;
-        st->ensure_pinned(bytes);
-        return (uint8_t*)st->pinned[0];
-      });
+      // split decode: the pinned buffer holds [descriptor | tables | coefficients]
+      JpegLayout lay;
+      if (jpeg_gpu_) {
+        lay = decode_jpeg_coeffs(jpeg.data(), jpeg.size(), [&](size_t n) {
+          st->ensure_pinned(kJpegHeader + n * sizeof(int16_t));
+          return (int16_t*)((uint8_t*)st->pinned[0] + kJpegHeader);
+        });
+        on_gpu = jpeg_gpu_supported(lay);  // other layouts: the host decoder below
+      }
+      if (on_gpu) {
+        img_w = lay.width;
+        img_h = lay.height;
+        bytes = (size_t)img_w * img_h * 3;
+      } else {
+        decode_jpeg_into(jpeg.data(), jpeg.size(), [&](int w, int h) {
+          img_w = w;
+          img_h = h;
+          bytes = (size_t)w * h * 3;
+          st->ensure_pinned(bytes);
+          return (uint8_t*)st->pinned[0];
+        });
+      }
       hipStream_t s = st->stream(home);
       DMLC_HIP_CHECK(hipSetDevice(home));
       // plain hipMalloc: peer-mapped for the other GPUs' resize kernels
       // (stream-ordered pool memory would need per-pool access grants)
       DMLC_HIP_CHECK(hipMalloc(&dev, std::max<size_t>(bytes, 256)));
-      DMLC_HIP_CHECK(hipMemcpyAsync(dev, st->pinned[0], bytes, hipMemcpyHostToDevice, s));
+      if (on_gpu) {
+        // one upload, then the two kernels write the image straight into its
+        // cache block: no RGB crosses PCIe
+        const size_t ncoef = lay.total(), in_bytes = kJpegHeader + ncoef * sizeof(int16_t);
+        const size_t plane_bytes = jpeg_plane_bytes(lay);
+        auto& js = st->jpeg_scratch(home, in_bytes, plane_bytes);
+        uint8_t* hp = (uint8_t*)st->pinned[0];
+        auto* hd = (JpegGpuImage*)hp;
+        *hd = jpeg_gpu_image(lay, (uint8_t*)dev, 0, 0, 0);
+        jpeg_gpu_tables(lay, (float*)(hp + kJpegTables));
+        uint8_t* din = (uint8_t*)js.in;
+        DMLC_HIP_CHECK(hipMemcpyAsync(din, hp, in_bytes, hipMemcpyHostToDevice, s));
+        jpeg_idct_planes(hd, (const JpegGpuImage*)din, 1, (const float*)(din + kJpegTables), lay.ncomp,
+                         (const int16_t*)(din + kJpegHeader), ncoef, (uint8_t*)js.planes, js.plane_bytes, s);
+        jpeg_planes_to_rgb(hd, (const JpegGpuImage*)din, 1, (const uint8_t*)js.planes, js.plane_bytes, s);
+      } else {
+        DMLC_HIP_CHECK(hipMemcpyAsync(dev, st->pinned[0], bytes, hipMemcpyHostToDevice, s));
+      }
       DMLC_HIP_CHECK(hipStreamSynchronize(s));  // resident before it is visible
     } catch (...) {
       give_stager(st);
@@ -928,6 +996,7 @@ class GpuExecutor : public Executor {
       return;
     }
     if (count_as_miss) ++stats_.misses; else ++stats_.staged;
+    if (on_gpu) ++stats_.jpeg_gpu; else ++stats_.jpeg_cpu;
     // evict least-recently-used entries no query has pinned
     auto victim = lru_.end();
     while (cache_bytes_ + bytes > cache_cap_ && victim != lru_.begin()) {
@@ -957,6 +1026,7 @@ class GpuExecutor : public Executor {
 
   std::vector<int> devices_;
   int max_batch_, lanes_;
+  const bool jpeg_gpu_;
   std::set<std::pair<int, int>> peers_;  // (reader, owner) with peer access enabled
   std::unique_ptr<dp::Fleet> fleet_;
   std::mutex weights_mu_;
@@ -977,13 +1047,14 @@ class GpuExecutor : public Executor {
 }  // namespace
 
 std::unique_ptr<Executor> make_executor(const std::string& backend, const std::vector<int>& devices, int max_batch,
-                                        size_t cache_bytes, int min_shard, int lanes, int batch_window_us) {
+                                        size_t cache_bytes, int min_shard, int lanes, int batch_window_us,
+                                        bool jpeg_gpu) {
   std::string b = backend;
   if (b == "auto") b = hip_device_count() > 0 ? "gpu" : "cpu";
   if (b == "gpu") {
     for (int d : devices)
       if (d < 0 || hip_device_count() <= d) throw std::runtime_error("no HIP device " + std::to_string(d));
-    return std::make_unique<GpuExecutor>(devices, max_batch, cache_bytes, min_shard, lanes, batch_window_us);
+    return std::make_unique<GpuExecutor>(devices, max_batch, cache_bytes, min_shard, lanes, batch_window_us, jpeg_gpu);
   }
   if (b == "cpu") return std::make_unique<CpuExecutor>();
   throw std::invalid_argument("unknown executor backend: " + backend);

@@ -31,6 +31,9 @@ struct Prediction {
 struct CacheStats {
   uint64_t hits = 0, misses = 0, staged = 0, evictions = 0;
   uint64_t bytes = 0, entries = 0, capacity = 0;
+  // images decoded into the cache by each path: split decode finished on the
+  // GPU (make_executor's jpeg_gpu) / the host decoder
+  uint64_t jpeg_gpu = 0, jpeg_cpu = 0;
 };
 
 class Executor {
@@ -101,8 +104,14 @@ std::unique_ptr<Executor> make_executor(const std::string& backend, int device, 
 // batch_window_us: concurrent queries to one (model, GPU) instance are
 // coalesced into one forward of up to max_batch images; a queued query waits
 // at most this long for others to join (dp::FleetOptions).
+// jpeg_gpu (GPU executor, off by default): an image missing from the HBM cache
+// is only entropy-decoded on the host (decode_jpeg_coeffs); its coefficients
+// are uploaded and the inverse DCT and colour conversion run on its home GPU
+// (csrc/kernels/jpeg_finish.hip) straight into its cache block. Layouts the
+// kernels do not handle keep the host decoder.
 std::unique_ptr<Executor> make_executor(const std::string& backend, const std::vector<int>& devices, int max_batch,
-                                        size_t cache_bytes, int min_shard, int lanes = 2, int batch_window_us = 200);
+                                        size_t cache_bytes, int min_shard, int lanes = 2, int batch_window_us = 200,
+                                        bool jpeg_gpu = false);
 int hip_device_count();
 
 // Host-side reference preprocessing (same rule as csrc/kernels/preprocess.hip):

@@ -634,3 +634,118 @@ def softmax_top1(logits: torch.Tensor, n: int | None = None) -> tuple[torch.Tens
     prob = torch.empty(B, device=logits.device, dtype=torch.float32)
     native().softmax_top1(_ptr(logits.contiguous()), B, n, ld, _ptr(idx), _ptr(prob), _stream())
     return idx, prob
+
+
+# ---------------------------------------------------------------- split JPEG decode
+def _align(n: int, a: int = 256) -> int:
+    return (n + a - 1) // a * a
+
+
+def _upload(parts, device) -> tuple[torch.Tensor, list[int]]:
+    """numpy arrays -> ONE pinned staging buffer (each part 256-byte aligned)
+    -> one host-to-device copy on the current stream. Returns the device
+    buffer and the parts' byte offsets."""
+    import numpy as np
+    offs, total = [], 0
+    for p in parts:
+        offs.append(total)
+        total += _align(p.nbytes)
+    stage = torch.empty(max(total, 256), dtype=torch.uint8, pin_memory=True)
+    view = stage.numpy()
+    for p, o in zip(parts, offs):
+        view[o:o + p.nbytes] = np.ascontiguousarray(p).reshape(-1).view(np.uint8)
+    return stage.to(device, non_blocking=True), offs
+
+
+def jpeg_idct(coeffs, qt, bw: int, bh: int, device="cuda") -> torch.Tensor:
+    """Stage 1 of the GPU JPEG finish on one plane: quantised int16
+    coefficients [bh][bw][64] (natural order) and a quantisation table (64
+    values, natural order) -> the u8 plane [8 bh, 8 bw] (dequantise, AAN
+    inverse DCT in fp32, + 128, round half up, clamp)."""
+    import numpy as np
+    nat = native()
+    dev = coeffs.device if isinstance(coeffs, torch.Tensor) else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("dmlc.ops kernels need CUDA/HIP tensors (no CPU fallback)")
+    co = torch.as_tensor(coeffs).to(device=dev, dtype=torch.int16).contiguous().reshape(-1)
+    if co.numel() != bw * bh * 64:
+        raise ValueError("jpeg_idct: coeffs must hold bw * bh * 64 values")
+    layout = {"width": 8 * bw, "height": 8 * bh, "hmax": 1, "vmax": 1,
+              "comps": [{"h": 1, "v": 1, "bw": bw, "bh": bh, "qt": np.asarray(qt, dtype=np.uint16).reshape(64)}]}
+    descs, tables, ncoef, pbytes = nat.jpeg_gpu_plan([layout], [0])
+    with torch.cuda.device(dev):
+        d, (od, ot) = _upload([descs, tables], dev)
+        plane = torch.empty(8 * bh, 8 * bw, dtype=torch.uint8, device=dev)
+        nat.jpeg_idct_planes(descs, d.data_ptr() + od, d.data_ptr() + ot, tables.shape[0], co.data_ptr(), ncoef,
+                             plane.data_ptr(), pbytes, _stream())
+    return plane
+
+
+def jpeg_planes_to_rgb(planes, layout: dict, device="cuda") -> torch.Tensor:
+    """Stage 2 of the GPU JPEG finish on one image: its u8 component planes
+    ([8 bh, 8 bw] each) -> u8 [height, width, 3]; bit-identical to
+    ``native().ycc_planes_to_rgb`` on the same planes."""
+    nat = native()
+    if not nat.jpeg_gpu_supported(layout):
+        raise ValueError("jpeg_planes_to_rgb: unsupported layout")
+    ps = [torch.as_tensor(p) for p in planes]
+    dev = ps[0].device if ps[0].is_cuda else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("dmlc.ops kernels need CUDA/HIP tensors (no CPU fallback)")
+    comps = layout["comps"]
+    if len(ps) != len(comps):
+        raise ValueError("jpeg_planes_to_rgb: one plane per component")
+    for p, c in zip(ps, comps):
+        if p.dtype != torch.uint8 or tuple(p.shape) != (8 * c["bh"], 8 * c["bw"]):
+            raise ValueError("jpeg_planes_to_rgb: planes are uint8 [8 bh, 8 bw]")
+    H, W = layout["height"], layout["width"]
+    with torch.cuda.device(dev):
+        scratch = torch.cat([p.to(dev).reshape(-1) for p in ps])
+        rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+        descs, _, _, pbytes = nat.jpeg_gpu_plan([layout], [rgb.data_ptr()])
+        d, (od,) = _upload([descs], dev)
+        nat.jpeg_planes_to_rgb(descs, d.data_ptr() + od, scratch.data_ptr(), pbytes, _stream())
+    return rgb
+
+
+def jpeg_decode(blobs, device="cuda") -> list[torch.Tensor]:
+    """JPEG files (bytes) -> u8 HWC tensors on ``device``: Huffman decoding on
+    the host, then ONE upload (descriptors, tables and coefficients of the
+    whole list) and ONE launch pair (inverse DCT, colour) for the whole ragged
+    list. An image whose layout the GPU path does not handle
+    (``native().jpeg_gpu_supported``) is decoded by the CPU decoder and
+    uploaded as pixels."""
+    import numpy as np
+    nat = native()
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("dmlc.ops kernels need CUDA/HIP tensors (no CPU fallback)")
+    out: list = [None] * len(blobs)
+    which, layouts, coefs = [], [], []
+    for i, b in enumerate(blobs):
+        b = bytes(b)
+        lay, co = nat.decode_jpeg_coeffs(b)
+        if nat.jpeg_gpu_supported(lay):
+            which.append(i)
+            layouts.append(lay)
+            coefs.append(co)
+        else:
+            out[i] = torch.from_numpy(nat.decode_jpeg(b)).to(dev)
+    if not which:
+        return out
+    with torch.cuda.device(dev):
+        offs, total = [], 0
+        for lay in layouts:
+            offs.append(total)
+            total += _align(lay["height"] * lay["width"] * 3)
+        rgb = torch.empty(total, dtype=torch.uint8, device=dev)
+        descs, tables, ncoef, pbytes = nat.jpeg_gpu_plan(layouts, [rgb.data_ptr() + o for o in offs])
+        d, (od, ot, oc) = _upload([descs, tables, np.concatenate(coefs)], dev)
+        planes = torch.empty(pbytes, dtype=torch.uint8, device=dev)
+        nat.jpeg_idct_planes(descs, d.data_ptr() + od, d.data_ptr() + ot, tables.shape[0], d.data_ptr() + oc, ncoef,
+                             planes.data_ptr(), pbytes, _stream())
+        nat.jpeg_planes_to_rgb(descs, d.data_ptr() + od, planes.data_ptr(), pbytes, _stream())
+    for i, lay, o in zip(which, layouts, offs):
+        h, w = lay["height"], lay["width"]
+        out[i] = rgb[o:o + h * w * 3].view(h, w, 3)
+    return out
