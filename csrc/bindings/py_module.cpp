@@ -516,6 +516,26 @@ PYBIND11_MODULE(_C, m) {
     return py::make_tuple(out, total);
   }, py::arg("arch"), py::arg("weights"), py::arg("options") = std::map<std::string, bool>{},
      py::arg("num_classes") = 1000, py::arg("image_size") = 224);
+  // host-only launch plan of a graph-captured forward: [(kernel, first op, n_ops, detail)], and the graph's ops
+  // in Engine.op_list's format
+  auto plan_list = [](const std::vector<Engine::PlanLine>& lines) {
+    py::list out;
+    for (const auto& l : lines) out.append(py::make_tuple(l.kernel, l.first_op, l.n_ops, l.detail));
+    return out;
+  };
+  auto op_list = [](const std::vector<Op>& ops) {
+    py::list l;
+    for (const auto& op : ops) l.append(py::make_tuple(op.name, op.in, op.out, op.res));
+    return l;
+  };
+  m.def("plan_audit", [=](const std::string& arch, const py::dict& weights, const std::map<std::string, bool>& options,
+                          int B, bool native, int num_cus, int num_classes, int image_size) {
+    std::vector<Op> ops;
+    const auto lines = Engine::plan_audit(arch, to_weight_map(weights), engine_options(options), B, native, num_cus,
+                                          &ops, num_classes, image_size);
+    return py::make_tuple(plan_list(lines), op_list(ops));
+  }, py::arg("arch"), py::arg("weights"), py::arg("options") = std::map<std::string, bool>{}, py::arg("B") = 256,
+     py::arg("native") = true, py::arg("num_cus") = 256, py::arg("num_classes") = 1000, py::arg("image_size") = 224);
   py::class_<Engine>(m, "Engine")
       .def(py::init([](const std::string& arch, const py::dict& weights, int device, int num_classes,
                        int image_size, const std::map<std::string, bool>& options) {
@@ -552,12 +572,9 @@ PYBIND11_MODULE(_C, m) {
              auto s = e.activation_shape(id);
              return py::make_tuple(s.H, s.W, s.C, s.f32);
            })
-      .def("op_list",
-           [](const Engine& e) {
-             py::list l;
-             for (const auto& op : e.ops()) l.append(py::make_tuple(op.name, op.in, op.out, op.res));
-             return l;
-           })
+      .def("op_list", [=](const Engine& e) { return op_list(e.ops()); })
+      .def("plan", [=](const Engine& e, int B, int Hin, int Win) { return plan_list(e.plan_lines(e.plan(B, Hin, Win))); })
+      .def_property_readonly("num_cus", &Engine::num_cus)
       .def_property_readonly("num_activations", &Engine::num_activations)
       .def_property_readonly("arch", &Engine::arch)
       .def_property_readonly("device", &Engine::device)

@@ -160,6 +160,16 @@ std::vector<PackRegion> Engine::pack_audit(const std::string& arch, const Weight
   return regions;
 }
 
+std::vector<Engine::PlanLine> Engine::plan_audit(const std::string& arch, const WeightMap& weights,
+                                                 const EngineOptions& options, int B, bool native, int num_cus,
+                                                 std::vector<Op>* engine_ops, int num_classes, int image_size) {
+  Engine e(HostOnly{}, arch, weights, num_classes, image_size, options);
+  e.num_cus_ = num_cus;
+  e.layout_weights();
+  if (engine_ops) *engine_ops = e.ops_;
+  return e.plan_lines(e.plan(B, native, options.fork_ds, false));
+}
+
 // Same graph, packing and calibration as `src`, on another device, with an
 // uninitialised weight arena: the caller fills it (an RCCL broadcast of the
 // source arena, GpuExecutor::ModelSlot). The host packing runs once per model
@@ -199,8 +209,7 @@ void Engine::init_device() {
     DMLC_HIP_CHECK(hipEventCreateWithFlags(&fork_evs_[i], hipEventDisableTiming));
     DMLC_HIP_CHECK(hipEventCreateWithFlags(&join_evs_[i], hipEventDisableTiming));
   }
-  ws_elems_ = (size_t)16 << 20;  // 64 MB split-K workspace
-  DMLC_HIP_CHECK(hipMalloc(&ws_, ws_elems_ * sizeof(float)));
+  DMLC_HIP_CHECK(hipMalloc(&ws_, kSplitKWsElems * sizeof(float)));
   DMLC_HIP_CHECK(hipMalloc(&zero_, 256));
   DMLC_HIP_CHECK(hipMemset(zero_, 0, 256));
 }
@@ -538,8 +547,9 @@ void Engine::pack_weights(const WeightMap& w) {
   DMLC_HIP_CHECK(hipMemcpy(warena_, host.data(), weight_bytes_, hipMemcpyHostToDevice));
 }
 
-std::vector<uint8_t> Engine::pack_host(const WeightMap& w, std::vector<PackRegion>* regions) {
-  // Layout pass.
+// Layout pass: every layer's padded sizes and the offsets of its regions in
+// the weight arena (all the planner reads of the packing).
+void Engine::layout_weights() {
   size_t off = 0;
   for (auto& L : convs_) {
     L.npad = conv_npad(L.cout);
@@ -555,38 +565,34 @@ std::vector<uint8_t> Engine::pack_host(const WeightMap& w, std::vector<PackRegio
     }
     L.wf_off = 0;
     L.wf_bytes = 0;
-    // (3x3 convs the register-weight stream conv runs, and the 1x1/s2
-    // downsample it fuses next to a stride-2 one)
-    // (and every 3x3/p1 conv and 1x1/s2 downsample the query-batch conv can
-    // run: conv_small.hip)
-    const bool small =
-        !L.fp8 && !L.fc && !L.pair && !L.stem_pool && L.in_act >= 0 && L.cout % 32 == 0 &&
-        ((L.kh == 3 && L.kw == 3 && L.pad == 1) || (L.kh == 1 && L.kw == 1 && L.stride == 2 && L.pad == 0)) &&
-        conv_small_supported(shapes_[L.in_act].H, shapes_[L.in_act].W, shapes_[L.in_act].C, L.cout, L.stride);
-    if (small || (!L.fp8 && !L.fc && !L.pair && !L.stem_pool && L.in_act >= 0 && L.cout % 32 == 0 && L.kpad % 32 == 0 &&
-        (((L.kh == 3 && L.kw == 3) || (L.kh == 1 && L.kw == 1 && L.stride == 2)) &&
-             (conv3x3_stream_uses_frag(shapes_[L.in_act].H, shapes_[L.in_act].W, shapes_[L.in_act].C, L.cout,
-                                       L.stride) ||
-              (L.stride == 2 &&
-               conv3x3_s2rows_supported(shapes_[L.in_act].H, shapes_[L.in_act].W, shapes_[L.in_act].C, L.cout)) ||
-              (L.kh == 3 && L.stride == 1 && L.pad == 1 &&
-               conv3x3_rows28_supported(shapes_[L.in_act].H, shapes_[L.in_act].W, shapes_[L.in_act].C, L.cout))) ||
-         (L.kh == 3 && L.kw == 3 && L.stride == 1 && L.pad == 1 &&
-          (conv3x3_rows_supported(shapes_[L.in_act].H, shapes_[L.in_act].W, shapes_[L.in_act].C, L.cout) ||
-           conv3x3_13_supported(shapes_[L.in_act].H, shapes_[L.in_act].W, shapes_[L.in_act].C, L.cout)))))) {
-      L.wf_off = off;  // fragment-order copy for the register-weight stream conv
+    // Who gets a bf16 fragment-order copy: the plain 3x3/p1 convs and 1x1/s2
+    // downsamples that a kernel reading its weights in that order can run.
+    const ActShape is = L.in_act >= 0 ? shapes_[L.in_act] : ActShape{};
+    const bool conv_or_ds = (L.plain_3x3() || L.plain_ds2()) && L.cout % 32 == 0;
+    // every one the query-batch conv can run (conv_small.hip)
+    const bool small = conv_or_ds && conv_small_supported(is.H, is.W, is.C, L.cout, L.stride);
+    // the register-weight stream conv with the downsample it fuses next to a
+    // stride-2 one, and layer2.0's pair on conv3x3_s2rows
+    const bool stream = conv_or_ds && (conv3x3_stream_uses_frag(is.H, is.W, is.C, L.cout, L.stride) ||
+                                       (L.stride == 2 && conv3x3_s2rows_supported(is.H, is.W, is.C, L.cout)));
+    // the stride-1 row kernels and AlexNet's 13x13 convs
+    const bool rows = L.plain_3x3() && L.cout % 32 == 0 && L.stride == 1 &&
+                      (conv3x3_rows28_supported(is.H, is.W, is.C, L.cout) ||
+                       conv3x3_rows_supported(is.H, is.W, is.C, L.cout) ||
+                       conv3x3_13_supported(is.H, is.W, is.C, L.cout));
+    if (small || ((stream || rows) && L.kpad % 32 == 0)) {
+      L.wf_off = off;
       L.wf_bytes = (size_t)L.cout * L.kpad * 2;
       off = align_up(off + L.wf_bytes, 256);
     }
-    if (!L.fp8 && !L.fc && L.in_act >= 0 && L.kh == 5 && L.kw == 5 && L.stride == 1 &&
-        conv5x5_27_supported(shapes_[L.in_act].H, shapes_[L.in_act].W, shapes_[L.in_act].C, L.cout, L.pad)) {
+    if (L.plain() && L.kh == 5 && L.kw == 5 && L.stride == 1 &&
+        conv5x5_27_supported(is.H, is.W, is.C, L.cout, L.pad)) {
       L.wf_off = off;  // fragment-order copy for conv5x5_27.hip
       L.wf_bytes = (size_t)L.cout * L.kpad * 2;
       off = align_up(off + L.wf_bytes, 256);
     }
     if (L.fp8 && !L.fc && L.in_act >= 0 && L.kh == 3 && L.kw == 3 && L.pad == 1 && L.kpad == 9 * L.cin &&
-        conv3x3_stream8_supported(shapes_[L.in_act].H, shapes_[L.in_act].W, shapes_[L.in_act].C, L.cout,
-                                  L.stride)) {
+        conv3x3_stream8_supported(is.H, is.W, is.C, L.cout, L.stride)) {
       L.wf_off = off;  // e4m3 fragment-order copy for conv3x3_stream8.hip
       L.wf_bytes = (size_t)L.cout * L.kpad;
       off = align_up(off + L.wf_bytes, 256);
@@ -630,7 +636,11 @@ std::vector<uint8_t> Engine::pack_host(const WeightMap& w, std::vector<PackRegio
     }
   }
   weight_bytes_ = off;
-  std::vector<uint8_t> host(off, 0);
+}
+
+std::vector<uint8_t> Engine::pack_host(const WeightMap& w, std::vector<PackRegion>* regions) {
+  layout_weights();
+  std::vector<uint8_t> host(weight_bytes_, 0);
   auto region = [&](const ConvLayer& L, const char* kind, size_t roff, size_t bytes) {
     if (roff + bytes > host.size())
       throw std::runtime_error("pack_weights: " + std::string(kind) + " region of " + L.name + " past the arena");
@@ -811,7 +821,7 @@ void Engine::reserve(int max_batch) {
   long slabs = 0;
   for (const Op& op : ops_) {
     if (op.type != OpType::Conv) continue;
-    const ConvArgs a = conv_args(op, max_batch, nullptr);
+    const ConvArgs a = conv_geom(op, max_batch);
     const int cfg = opt_.bigtile ? conv_bigtile_pick(a, num_cus_) : -1;
     if (cfg >= 0) slabs = std::max(slabs, conv_bigtile_slabs(a, cfg, conv_bigtile_splits(a, cfg, num_cus_)));
   }
@@ -833,18 +843,24 @@ double Engine::gflop_per_image() const {
   return f * 1e-9;
 }
 
-ConvArgs Engine::conv_args(const Op& op, int B, float* logits) const {
+namespace {
+// conv1x1.hip's *_supported checks read res, x2 and the chained reduce's
+// alpha / bias / w / y only as "the launch has this operand". A geometry has
+// no operands yet, so conv_geom marks the ones the layer has with this; bind()
+// replaces every one of them.
+alignas(16) char g_operand[16];
+}  // namespace
+
+ConvArgs Engine::conv_geom(const Op& op, int B) const {
   const ConvLayer& L = convs_[op.conv];
   const ActShape& is = shapes_[op.in];
   const ActShape& os = shapes_[op.out];
   ConvArgs a;
-  a.x = acts_[op.in];
-  a.zero = zero_;
+  a.w = a.y = g_operand;
+  a.bias = (const float*)g_operand;
+  if (op.res >= 0) a.res = g_operand;
+  if (L.fp8) a.alpha = (const float*)g_operand;
   a.stem = L.pair;
-  a.w = (const uint8_t*)warena_ + L.w_off;
-  a.bias = (const float*)((const uint8_t*)warena_ + L.b_off);
-  a.res = op.res >= 0 ? acts_[op.res] : nullptr;
-  a.y = (os.f32 && logits) ? (void*)logits : acts_[op.out];
   a.B = B;
   if (L.fc) {
     a.H = a.W = 1;
@@ -868,7 +884,6 @@ ConvArgs Engine::conv_args(const Op& op, int B, float* logits) const {
   a.out_f32 = os.f32;
   a.in_fp8 = L.fp8;
   a.out_fp8 = os.fp8;
-  if (L.fp8) a.alpha = (const float*)((const uint8_t*)warena_ + L.a_off);
   if (op.res >= 0 && shapes_[op.res].fp8) a.res_scale = shapes_[op.res].scale;
   if (os.fp8) a.out_inv_scale = 1.f / os.scale;
   int s = conv_pick_split_k(a, num_cus_);
@@ -881,652 +896,755 @@ ConvArgs Engine::conv_args(const Op& op, int B, float* logits) const {
     const int k_tiles = L.kpad / 64;
     s = std::max(1, std::min({k_tiles / 2, (num_cus_ / 2 + tiles - 1) / tiles, 32}));
   }
-  while (s > 1 && (size_t)s * M * L.npad > ws_elems_) --s;
+  while (s > 1 && (size_t)s * M * L.npad > kSplitKWsElems) --s;
   a.split_k = s;
-  a.ws = ws_;
   a.persistent = opt_.persistent;
   a.max_blocks = 2 * num_cus_;
   return a;
 }
 
-Engine::ConvPath Engine::conv_path(const Op& op, int B) const {
+void Engine::bind(ConvArgs& a, const Op& op, float* logits) const {
   const ConvLayer& L = convs_[op.conv];
-  const ActShape& is = shapes_[op.in];
-  const bool k3b = !L.fc && !L.pair && !L.fp8 && L.kh == 3 && L.kw == 3 && L.pad == 1 && !shapes_[op.out].f32;
-  const bool k3 = k3b && !shapes_[op.out].fp8;
-  // e4m3 output (fp8_3x3_out): the row / stream kernels' e4m3 epilogue
-  const bool k3o8 = k3b && shapes_[op.out].fp8 && opt_.fp8_3x3_out && op.res < 0;
-  // the stream conv runs 1-4 workgroups per image (or image pair): only
-  // worth it once the batch fills the CUs
-  // 14x14x256 -> 7x7x512 / s2 (layer4.0.conv1) runs 2 rounds of single-image
-  // workgroups with 49 of 64 fragment rows live: with the LDS weight ring and
-  // the fused downsample 67.9 us vs 44.2 + 13.3 us as two implicit GEMMs; with
-  // register weights 48.1 vs 13.2 + 46.3 us (profiles/r1_fused_ds.txt)
-  const bool l4s2 = L.stride == 2 && is.H < 28 && !(opt_.stream_l4s2 && opt_.stream_wreg);
-  const bool l1 = L.stride == 1 && is.C == 64;  // layer1: conv3x3_rows (the stream conv measured slower there)
-  // layer2's stride-1 convs: one weight-stationary workgroup per image walking
-  // its rows (59-60 us vs 62-66 us for the stream conv at B=256,
-  // profiles/r2_rows28.txt), once the batch fills >= ~70% of one round
-  const int rounds = (B + num_cus_ - 1) / num_cus_;
-  // query batches: one launch per conv, no split-K (conv_small.hip)
-  if (opt_.small_conv && k3 && L.wf_off && B <= kSmallConvMaxB &&
-      conv_small_supported(is.H, is.W, is.C, L.cout, L.stride) &&
-      !(opt_.direct13 && conv3x3_13_supported(is.H, is.W, is.C, L.cout)))  // (AlexNet keeps its fused pools)
-    return ConvPath::Small;
-  if (opt_.rows28 && (k3 || k3o8) && L.stride == 1 && L.wf_off && 10 * B >= 7 * rounds * num_cus_ &&
-      conv3x3_rows28_supported(is.H, is.W, is.C, L.cout))
-    return ConvPath::Rows28;
-  if (opt_.direct13 && k3 && L.stride == 1 && L.wf_off && conv3x3_13_supported(is.H, is.W, is.C, L.cout))
-    return ConvPath::Direct13;
-  // e4m3 in and out (fp8_3x3_in): whole images per workgroup, once the batch
-  // fills the CUs (query batches: the e4m3 implicit GEMM)
-  if (L.fp8 && !L.fc && L.kh == 3 && L.kw == 3 && L.pad == 1 && L.wf_off && op.res < 0 && shapes_[op.out].fp8 &&
-      4 * B >= num_cus_ && conv3x3_stream8_supported(is.H, is.W, is.C, L.cout, L.stride))
-    return ConvPath::Stream8;
-  if (opt_.direct27 && !L.fc && !L.fp8 && L.kh == 5 && L.kw == 5 && L.stride == 1 && L.relu && L.wf_off &&
-      L.kpad == 1600 && !shapes_[op.out].f32 && conv5x5_27_supported(is.H, is.W, is.C, L.cout, L.pad))
-    return ConvPath::Direct27;
-  if (opt_.stream_conv && (k3 || k3o8) && !l4s2 && !l1 && 8 * B >= num_cus_ &&
-      conv3x3_stream_supported(is.H, is.W, is.C, L.cout, L.stride))
-    return ConvPath::Stream;
-  if (opt_.row_conv && k3 && L.stride == 1 && conv3x3_rows_supported(is.H, is.W, is.C, L.cout)) return ConvPath::Rows;
-  if (opt_.conv1x1 && !L.fc && L.kh == 1 && L.kw == 1) {
-    ConvArgs a = conv_args(op, B, nullptr);
-    a.split_k = 1;
-    if (conv1x1_supported(a)) return ConvPath::OneByOne;
-  }
-  if (opt_.fc_gemm && L.fc && !L.fp8) {
-    const ConvArgs a = conv_args(op, B, nullptr);
-    if (fc_gemm_supported(a) && (size_t)B * L.npad <= ws_elems_) return ConvPath::Fc;
-  }
-  if (opt_.bigtile && conv_bigtile_pick(conv_args(op, B, nullptr), num_cus_) >= 0) return ConvPath::BigTile;
-  return ConvPath::Igemm;
-}
-
-bool Engine::head_fusable(size_t oi) const {
-  if (!opt_.fused_head || oi + 2 >= ops_.size()) return false;
-  const Op& pool = ops_[oi];
-  const Op& fc = ops_[oi + 1];
-  const Op& sm = ops_[oi + 2];
-  if (pool.type != OpType::AvgPoolGlobal || fc.type != OpType::Conv || sm.type != OpType::SoftmaxTop1) return false;
-  if (fc.in != pool.out || sm.in != fc.out || !shapes_[fc.out].f32 || shapes_[pool.out].fp8) return false;
-  const ConvLayer& L = convs_[fc.conv];
-  // (an e4m3 pool input, ResNet50 fp8: pooled from e4m3 in the head, C >= 2048)
-  if (shapes_[pool.in].fp8 && shapes_[pool.in].C < 2048) return false;
-  return L.fc && !L.fp8 && !L.relu && L.cin == shapes_[pool.in].C && head_supported(L.cin, L.cout, L.kpad, L.npad);
-}
-
-// ops[oi] is the last conv (stream path, whole-image workgroups) and
-// ops[oi+1] the global average pool, the only reader of its output: the
-// conv's epilogue writes the pooled bf16 vectors straight into the pool's
-// output activation and skips storing its own.
-bool Engine::pool_fusable(size_t oi, int B) const {
-  if (!opt_.fused_pool || oi + 1 >= ops_.size()) return false;
-  const Op& c = ops_[oi];
-  const Op& p = ops_[oi + 1];
-  if (c.type != OpType::Conv || p.type != OpType::AvgPoolGlobal || p.in != c.out) return false;
-  if (shapes_[p.out].fp8 || shapes_[p.out].f32 || shapes_[p.in].fp8) return false;
-  for (size_t j = 0; j < ops_.size(); ++j)
-    if (j != oi + 1 && (ops_[j].in == c.out || ops_[j].res == c.out)) return false;
-  const ConvLayer& L = convs_[c.conv];
-  const ActShape& is = shapes_[c.in];
-  return !L.fp8 && !shapes_[c.out].fp8 && conv_path(c, B) == ConvPath::Stream &&
-         conv3x3_stream_pool_supported(is.H, is.W, is.C, L.cout, L.stride);
-}
-
-// ops[oi] is a block's downsample (1x1/s2, BN, no ReLU) and ops[oi+1] the
-// block's 3x3/s2 conv1 on the same input, run by the stream conv.
-bool Engine::ds_fusable(size_t oi, int B) const {
-  if (oi + 1 >= ops_.size()) return false;
-  const Op& d = ops_[oi];
-  const Op& c = ops_[oi + 1];
-  if (d.type != OpType::Conv || c.type != OpType::Conv || d.in != c.in) return false;
-  const ConvLayer& D = convs_[d.conv];
-  const ConvLayer& L = convs_[c.conv];
-  return !D.fc && !D.fp8 && D.kh == 1 && D.kw == 1 && D.stride == 2 && D.pad == 0 && !D.relu && d.res < 0 &&
-         D.cout == L.cout && L.stride == 2 && !shapes_[d.out].fp8 && !shapes_[d.out].f32 &&
-         (conv_path(c, B) == ConvPath::Stream || (conv_path(c, B) == ConvPath::Small && D.wf_off));
-}
-
-// ops[oi], ops[oi+1] = conv1 (+ReLU) and conv2 (+identity residual, ReLU) of
-// a 56x56x64 basic block, both on the register-weight row conv, and conv1's
-// output read by nothing else: conv3x3_block runs the pair with the
-// intermediate kept in LDS (not written to its activation).
-bool Engine::block_fusable(size_t oi, int B) const {
-  if (!opt_.fused_block || !opt_.rows_wreg || oi + 1 >= ops_.size()) return false;
-  // one workgroup per image walks all 56 rows (~100 us per round of num_cus
-  // images at B=256 vs ~2 x 72 us for the two row convs, which split images
-  // into strips): only worth it with rounds that are >= ~70% full (B=1: 86 us
-  // fused vs ~30 us as strips; profiles/r2_block_kernel_stats.txt)
-  const int rounds = (B + num_cus_ - 1) / num_cus_;
-  if (10 * B < 7 * rounds * num_cus_) return false;
-  const Op& c1 = ops_[oi];
-  const Op& c2 = ops_[oi + 1];
-  if (c1.type != OpType::Conv || c2.type != OpType::Conv || c2.in != c1.out || c1.res >= 0 || c2.res != c1.in)
-    return false;
-  if (c1.side || c2.side) return false;
-  for (size_t j = 0; j < ops_.size(); ++j)
-    if (j != oi + 1 && (ops_[j].in == c1.out || ops_[j].res == c1.out)) return false;
-  const ConvLayer& L1 = convs_[c1.conv];
-  const ConvLayer& L2 = convs_[c2.conv];
-  const ActShape& is = shapes_[c1.in];
-  return L1.relu && L2.relu && L1.wf_off && L2.wf_off && conv3x3_block_supported(is.H, is.W, is.C) &&
-         L1.cout == is.C && L2.cout == is.C && !shapes_[c1.in].fp8 && !shapes_[c2.out].fp8 &&
-         conv_path(c1, B) == ConvPath::Rows && conv_path(c2, B) == ConvPath::Rows;
+  const uint8_t* wa = (const uint8_t*)warena_;
+  a.x = acts_[op.in];
+  a.zero = zero_;
+  a.w = wa + L.w_off;
+  a.bias = (const float*)(wa + L.b_off);
+  a.res = op.res >= 0 ? acts_[op.res] : nullptr;
+  a.y = (a.out_f32 && logits) ? (void*)logits : acts_[op.out];
+  a.alpha = L.fp8 ? (const float*)(wa + L.a_off) : nullptr;
+  a.ws = ws_;
 }
 
 // A resnet50_fp8 layer1 identity bottleneck's expand conv (1x1, 64 -> 256 on
 // 56x56, bf16 in, e4m3 out): bottleneck56.hip reads its weights in fragment order.
 bool Engine::bottleneck_conv3(const ConvLayer& L) const {
-  if (L.fc || L.fp8 || L.pair || L.stem_pool || L.in_act < 0 || L.kh != 1 || L.kw != 1 || L.stride != 1) return false;
+  if (!L.plain() || L.kh != 1 || L.kw != 1 || L.stride != 1) return false;
   const ActShape& is = shapes_[L.in_act];
   return fp8_ && is.C == 64 && L.cout == 256 && L.kpad == 64 && bottleneck56_supported(is.H, is.W, 256, 64);
 }
 
-// ops[oi..oi+2] = conv1 (1x1 256 -> 64, e4m3 in) + conv2 (3x3 64 -> 64) +
-// conv3 (1x1 64 -> 256 + the block input as residual, e4m3 out) of a
-// resnet50_fp8 layer1 identity block, the intermediates read by nothing else.
-bool Engine::bottleneck_fusable(size_t oi) const {
-  if (!opt_.fused_bottleneck || !fp8_ || oi + 2 >= ops_.size()) return false;
-  const Op& c1 = ops_[oi];
-  const Op& c2 = ops_[oi + 1];
-  const Op& c3 = ops_[oi + 2];
-  if (c1.type != OpType::Conv || c2.type != OpType::Conv || c3.type != OpType::Conv) return false;
-  if (c1.side || c2.side || c3.side || c2.in != c1.out || c3.in != c2.out || c1.res >= 0 || c2.res >= 0 ||
-      c3.res != c1.in)
-    return false;
-  const ConvLayer& L1 = convs_[c1.conv];
-  const ConvLayer& L2 = convs_[c2.conv];
-  const ConvLayer& L3 = convs_[c3.conv];
-  const ActShape& xs = shapes_[c1.in];
-  if (!xs.fp8 || !shapes_[c3.out].fp8 || shapes_[c1.out].fp8 || shapes_[c2.out].fp8) return false;
-  if (!bottleneck56_supported(xs.H, xs.W, xs.C, L1.cout) || !L1.fp8 || L1.kh != 1 || L1.stride != 1 || !L1.relu ||
-      L1.kpad != 256 || L1.npad != 64)
-    return false;
-  if (L2.kh != 3 || L2.kw != 3 || L2.stride != 1 || L2.pad != 1 || !L2.relu || L2.cout != 64 || !L2.wf_off ||
-      L2.kpad != 576)
-    return false;
-  if (!bottleneck_conv3(L3) || !L3.wf_off || !L3.relu) return false;
-  for (size_t j = 0; j < ops_.size(); ++j) {
-    if (j != oi + 1 && (ops_[j].in == c1.out || ops_[j].res == c1.out)) return false;
-    if (j != oi + 2 && (ops_[j].in == c2.out || ops_[j].res == c2.out)) return false;
-  }
-  return true;
+const char* kernel_name(Kernel k) {
+  static const char* const names[] = {
+      "None", "AlexStem", "StemPoolU8", "StemPool", "FcSmall", "Conv1x1Cat", "Conv1x1Chain", "Bottleneck56",
+      "Bottleneck56Head", "Block", "S2Rows", "S2Rows128", "Stream", "Stream8", "Rows28", "Rows", "Small", "Direct13",
+      "Direct27", "Conv1x1", "BigTile", "Igemm", "FcGemm", "HeadPooled", "HeadFused", "AvgPoolGlobal",
+      "AvgPoolAdaptive", "MaxPool", "Preprocess", "SoftmaxTop1"};
+  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::SoftmaxTop1 + 1, "one name per Kernel");
+  return names[(size_t)k];
 }
 
-bool Engine::bottleneck_head_fusable(size_t oi) const {
-  if (!opt_.fused_bottleneck || oi + 1 >= ops_.size()) return false;
-  const Op& c1 = ops_[oi];
-  const Op& c2 = ops_[oi + 1];
-  if (c1.type != OpType::Conv || c2.type != OpType::Conv || c1.side || c2.side || c2.in != c1.out || c1.res >= 0 ||
-      c2.res >= 0)
-    return false;
-  const ConvLayer& L1 = convs_[c1.conv];
-  const ConvLayer& L2 = convs_[c2.conv];
-  const ActShape& xs = shapes_[c1.in];
-  if (xs.fp8 || xs.f32 || shapes_[c1.out].fp8 || shapes_[c2.out].fp8 || shapes_[c2.out].f32) return false;
-  if (!bottleneck56_supported(xs.H, xs.W, 256, 64) || xs.C != 64) return false;
-  if (L1.fc || L1.fp8 || L1.pair || L1.stem_pool || L1.kh != 1 || L1.kw != 1 || L1.stride != 1 || !L1.relu ||
-      L1.cout != 64 || L1.kpad != 64 || L1.npad != 64)
-    return false;
-  if (L2.fp8 || L2.kh != 3 || L2.kw != 3 || L2.stride != 1 || L2.pad != 1 || !L2.relu || L2.cout != 64 ||
-      !L2.wf_off || L2.kpad != 576)
-    return false;
-  for (size_t j = 0; j < ops_.size(); ++j)
-    if (j != oi + 1 && (ops_[j].in == c1.out || ops_[j].res == c1.out)) return false;
-  return true;
-}
+// ---------------------------------------------------------------- planner
+// What to launch for one forward of B images: each conv op's kernel path
+// (once per plan), then one walk over the ops that decides which neighbours a
+// launch swallows. Reads the graph, the layout pass's offsets (wf_off,
+// cat_off, npad) and num_cus_; no device state.
+struct Engine::Planner {
+  enum class Path { Stream, Rows, Rows28, Direct13, Direct27, OneByOne, BigTile, Igemm, Small, Stream8, Fc };
 
-// ops[oi] is a downsample whose only reader is a later expand conv that
-// computes it itself (its cat_ds): that op's index, else -1.
-int Engine::ds_expand_op(size_t oi) const {
-  if (!opt_.ds_into_expand || ops_[oi].type != OpType::Conv) return -1;
-  const Op& d = ops_[oi];
-  int reader = -1;
-  for (size_t j = 0; j < ops_.size(); ++j) {
-    if (j == oi) continue;
-    if (ops_[j].in == d.out) return -1;
-    if (ops_[j].res == d.out) {
-      if (reader >= 0) return -1;
-      reader = (int)j;
+  const Engine& e;
+  const std::vector<Op>& ops;
+  const std::vector<ConvLayer>& convs;
+  const std::vector<ActShape>& shapes;
+  const EngineOptions& opt;
+  const int B, cus;
+  std::vector<Path> path;    // per conv op
+  std::vector<int> cat_ds;   // per op: the downsample op this expand conv computes itself (conv1x1 x2), or -1
+  std::vector<int> cat_by;   // per op: the expand conv that computes this downsample, or -1
+  std::vector<Step> steps;
+  int skip_ds = -1;     // downsample op left to the next op (the block's stride-2 conv1)
+  int ds_conv2 = -1;    // downsample op left to the block's conv2 (ds_into_conv2)
+  bool pooled = false;  // the last conv's epilogue wrote the global average pool
+
+  Planner(const Engine& eng, int batch)
+      : e(eng), ops(eng.ops_), convs(eng.convs_), shapes(eng.shapes_), opt(eng.opt_), B(batch), cus(eng.num_cus_),
+        path(ops.size(), Path::Igemm), cat_ds(ops.size(), -1), cat_by(ops.size(), -1) {
+    for (size_t i = 0; i < ops.size(); ++i) {
+      if (ops[i].type != OpType::Conv) continue;
+      path[i] = conv_path(ops[i]);
+      const int r = ds_expand_op(i);
+      cat_by[i] = r;
+      if (r > (int)i) cat_ds[r] = (int)i;
     }
   }
-  if (reader < 0) return -1;
-  const ConvLayer& L3 = convs_[ops_[reader].conv];
-  if (L3.cat_ds != d.conv || !L3.cat_off) return -1;
-  ConvArgs a = conv_args(ops_[reader], 1, nullptr);
-  a.split_k = 1;
-  a.res = nullptr;
-  a.x2 = acts_.empty() ? (const void*)16 : acts_[d.in];
-  a.cin2 = convs_[d.conv].cin;
-  a.Kpad = L3.kpad + convs_[d.conv].kpad;
-  return conv1x1_supported(a) ? reader : -1;
-}
 
-// The stride-2 conv1 of a block whose downsample it computes (fuse_ds) on
-// the 56x56x64 -> 128 shape: conv3x3_s2rows runs one workgroup per image
-// (59 us at B=256 vs 72 us for the stream conv's 4 rounds of strips,
-// profiles/r2_s2rows.txt); like the fused block only with rounds >= ~70% full.
-// ops[oi] = layer2.0.conv1 on conv3x3_s2rows (its downsample = ops[oi - 1]);
-// the block's conv2 (ops[oi + 1], on conv3x3_rows28) can compute that
-// downsample as 2 more K steps when it is the downsample output's only reader.
-bool Engine::ds_conv2_ok(size_t oi, int B) const {
-  if (!opt_.ds_into_conv2 || oi < 1 || oi + 1 >= ops_.size()) return false;
-  const Op& d = ops_[oi - 1];
-  const Op& c2 = ops_[oi + 1];
-  if (c2.type != OpType::Conv || c2.res != d.out || c2.in != ops_[oi].out) return false;
-  const ConvLayer& L2 = convs_[c2.conv];
-  const ConvLayer& D = convs_[d.conv];
-  if (!L2.wf_off || !D.wf_off || L2.fp8 || shapes_[c2.out].fp8 || conv_path(c2, B) != ConvPath::Rows28) return false;
-  const ActShape& xs = shapes_[d.in];
-  if (xs.H != 56 || xs.W != 56 || xs.C != 64 || xs.fp8 || xs.f32 || L2.cout != 128 || D.cout != 128) return false;
-  for (size_t j = 0; j < ops_.size(); ++j)
-    if (j != oi + 1 && (ops_[j].in == d.out || ops_[j].res == d.out)) return false;
-  return true;
-}
+  bool conv(size_t i) const { return i < ops.size() && ops[i].type == OpType::Conv; }
+  // the only reader of activation a is op j
+  bool only_reader(int a, size_t j) const {
+    for (size_t i = 0; i < ops.size(); ++i)
+      if (i != j && (ops[i].in == a || ops[i].res == a)) return false;
+    return true;
+  }
+  // one-workgroup-per-image kernels: only with rounds of num_cus images that are >= ~70% full
+  bool full_rounds() const { return 10 * B >= 7 * ((B + cus - 1) / cus) * cus; }
 
-// ops[oi] is a bottleneck's expand conv (1x1, residual) and ops[oi + 1] the
-// next bottleneck's reduce conv on its output, both on conv1x1.hip, in a form
-// conv1x1_chain runs as one launch (ResNet50 e4m3 layer2.0-2.2 -> 2.1-2.3).
-// The expand output keeps its other reader (the next expand's residual).
-bool Engine::chain_ok(size_t oi, int B) const {
-  if (!opt_.chain_1x1 || oi + 1 >= ops_.size() || acts_.empty()) return false;
-  const Op& e = ops_[oi];
-  const Op& r = ops_[oi + 1];
-  if (e.type != OpType::Conv || r.type != OpType::Conv || e.res < 0 || r.in != e.out || r.res >= 0 || e.side ||
-      r.side)
-    return false;
-  if (conv_path(e, B) != ConvPath::OneByOne || conv_path(r, B) != ConvPath::OneByOne) return false;
-  if (convs_[e.conv].cat_off) return false;  // (an expand with its downsample as a second K block)
-  ConvArgs a = conv_args(e, B, nullptr), ra = conv_args(r, B, nullptr);
-  a.split_k = ra.split_k = 1;
-  return conv1x1_chain_supported(a, ra);
-}
-
-bool Engine::s2rows_ok(const Op& op, const ConvLayer& D, int B) const {
-  const ConvLayer& L = convs_[op.conv];
-  const ActShape& is = shapes_[op.in];
-  const int rounds = (B + num_cus_ - 1) / num_cus_;
-  return opt_.s2rows && op.res < 0 && L.wf_off && D.wf_off && 10 * B >= 7 * rounds * num_cus_ &&
-         conv3x3_s2rows_supported(is.H, is.W, is.C, L.cout);
-}
-
-bool Engine::side_safe(int B) const {
-  for (const Op& op : ops_)
-    if (op.type == OpType::Conv && conv_path(op, B) == ConvPath::BigTile) return false;
-  return true;
-}
-
-void Engine::run_ops(const uint8_t* images, int B, int Hin, int Win, int32_t* idx, float* prob,
-                     float* logits, hipStream_t s, std::vector<hipEvent_t>* evs, bool trace) {
-  size_t ei = 0;
-  if (evs) DMLC_HIP_CHECK(hipEventRecord((*evs)[ei++], s));
-  // per-op event timing keeps every op on one stream
-  const bool side_ready = opt_.fork_ds && !evs && side_safe(B);
-  std::map<int, hipEvent_t> joined;  // activation -> event its side-stream producer recorded
-  int skip = 0;                      // ops already done by a fused kernel
-  int skip_ds = -1;                  // downsample op left to the next (stream) conv
-  int ds_conv2 = -1;                 // downsample op left to the block's conv2 (ds_into_conv2)
-  bool pooled = false;               // the last conv wrote pooled_ (fused avgpool)
-  for (size_t oi = 0; oi < ops_.size(); ++oi) {
-    const Op& op = ops_[oi];
-    if (skip > 0) {
-      --skip;
-      if (evs) DMLC_HIP_CHECK(hipEventRecord((*evs)[ei++], s));
-      continue;
+  Path conv_path(const Op& op) const {
+    const ConvLayer& L = convs[op.conv];
+    const ActShape& is = shapes[op.in];
+    const bool k3b = L.plain_3x3() && !shapes[op.out].f32;
+    const bool k3 = k3b && !shapes[op.out].fp8;
+    // e4m3 output (fp8_3x3_out): the row / stream kernels' e4m3 epilogue
+    const bool k3o8 = k3b && shapes[op.out].fp8 && opt.fp8_3x3_out && op.res < 0;
+    // the stream conv runs 1-4 workgroups per image (or image pair): only
+    // worth it once the batch fills the CUs
+    // 14x14x256 -> 7x7x512 / s2 (layer4.0.conv1) runs 2 rounds of single-image
+    // workgroups with 49 of 64 fragment rows live: with the LDS weight ring and
+    // the fused downsample 67.9 us vs 44.2 + 13.3 us as two implicit GEMMs; with
+    // register weights 48.1 vs 13.2 + 46.3 us (profiles/r1_fused_ds.txt)
+    const bool l4s2 = L.stride == 2 && is.H < 28 && !(opt.stream_l4s2 && opt.stream_wreg);
+    const bool l1 = L.stride == 1 && is.C == 64;  // layer1: conv3x3_rows (the stream conv measured slower there)
+    // query batches: one launch per conv, no split-K (conv_small.hip)
+    if (opt.small_conv && k3 && L.wf_off && B <= kSmallConvMaxB &&
+        conv_small_supported(is.H, is.W, is.C, L.cout, L.stride) &&
+        !(opt.direct13 && conv3x3_13_supported(is.H, is.W, is.C, L.cout)))  // (AlexNet keeps its fused pools)
+      return Path::Small;
+    // layer2's stride-1 convs: one weight-stationary workgroup per image walking
+    // its rows (59-60 us vs 62-66 us for the stream conv at B=256,
+    // profiles/r2_rows28.txt)
+    if (opt.rows28 && (k3 || k3o8) && L.stride == 1 && L.wf_off && full_rounds() &&
+        conv3x3_rows28_supported(is.H, is.W, is.C, L.cout))
+      return Path::Rows28;
+    if (opt.direct13 && k3 && L.stride == 1 && L.wf_off && conv3x3_13_supported(is.H, is.W, is.C, L.cout))
+      return Path::Direct13;
+    // e4m3 in and out (fp8_3x3_in): whole images per workgroup, once the batch
+    // fills the CUs (query batches: the e4m3 implicit GEMM)
+    if (L.fp8 && !L.fc && L.kh == 3 && L.kw == 3 && L.pad == 1 && L.wf_off && op.res < 0 && shapes[op.out].fp8 &&
+        4 * B >= cus && conv3x3_stream8_supported(is.H, is.W, is.C, L.cout, L.stride))
+      return Path::Stream8;
+    if (opt.direct27 && L.plain() && L.kh == 5 && L.kw == 5 && L.stride == 1 && L.relu && L.wf_off &&
+        L.kpad == 1600 && !shapes[op.out].f32 && conv5x5_27_supported(is.H, is.W, is.C, L.cout, L.pad))
+      return Path::Direct27;
+    if (opt.stream_conv && (k3 || k3o8) && !l4s2 && !l1 && 8 * B >= cus &&
+        conv3x3_stream_supported(is.H, is.W, is.C, L.cout, L.stride))
+      return Path::Stream;
+    if (opt.row_conv && k3 && L.stride == 1 && conv3x3_rows_supported(is.H, is.W, is.C, L.cout)) return Path::Rows;
+    if (opt.conv1x1 && !L.fc && L.kh == 1 && L.kw == 1) {
+      ConvArgs a = e.conv_geom(op, B);
+      a.split_k = 1;
+      if (conv1x1_supported(a)) return Path::OneByOne;
     }
-    std::optional<TraceRange> tr;  // per-op host ranges (not inside a graph capture)
-    if (trace) tr.emplace(op.name.c_str());
-    switch (op.type) {
-      case OpType::Preprocess: {
-        const bool paired = op.k == 1;
-        // AlexNet: 224x224 u8 images -> features.2's output in one kernel
-        if (oi + 2 < ops_.size() && ops_[oi + 1].type == OpType::Conv && ops_[oi + 2].type == OpType::MaxPool &&
-            convs_[ops_[oi + 1].conv].alex_stem && opt_.fused_preprocess && Hin == image_size_ &&
-            Win == image_size_) {
-          const ConvLayer& L = convs_[ops_[oi + 1].conv];
-          const uint8_t* wa = (const uint8_t*)warena_;
-          alex_stem_u8(images, wa + L.wf_off, (const float*)(wa + L.b_off), acts_[ops_[oi + 2].out], B, s);
-          skip = 2;
+    if (opt.fc_gemm && L.fc && !L.fp8 && fc_gemm_supported(e.conv_geom(op, B)) &&
+        (size_t)B * L.npad <= kSplitKWsElems)
+      return Path::Fc;
+    if (opt.bigtile && conv_bigtile_pick(e.conv_geom(op, B), cus) >= 0) return Path::BigTile;
+    return Path::Igemm;
+  }
+
+  // ops[oi] is a downsample whose only reader is a later expand conv that
+  // computes it itself (its cat_ds, the K-concat form of conv1x1): that op's
+  // index, else -1.
+  int ds_expand_op(size_t oi) const {
+    if (!opt.ds_into_expand) return -1;
+    const Op& d = ops[oi];
+    int reader = -1;
+    for (size_t j = 0; j < ops.size() && reader < 0; ++j)
+      if (j != oi && ops[j].res == d.out) reader = (int)j;
+    if (reader < 0 || ops[reader].in == d.out || !only_reader(d.out, reader)) return -1;
+    const ConvLayer& L3 = convs[ops[reader].conv];
+    if (L3.cat_ds != d.conv || !L3.cat_off) return -1;
+    const ConvLayer& D = convs[d.conv];
+    ConvArgs a = e.conv_geom(ops[reader], 1);
+    a.split_k = 1;
+    a.res = nullptr;
+    a.x2 = g_operand;
+    a.cin2 = D.cin;
+    a.Kpad = L3.kpad + D.kpad;
+    return conv1x1_supported(a) ? reader : -1;
+  }
+
+  bool head_fusable(size_t oi) const {
+    if (!opt.fused_head || oi + 2 >= ops.size()) return false;
+    const Op& pool = ops[oi];
+    const Op& fc = ops[oi + 1];
+    const Op& sm = ops[oi + 2];
+    if (pool.type != OpType::AvgPoolGlobal || fc.type != OpType::Conv || sm.type != OpType::SoftmaxTop1) return false;
+    if (fc.in != pool.out || sm.in != fc.out || !shapes[fc.out].f32 || shapes[pool.out].fp8) return false;
+    const ConvLayer& L = convs[fc.conv];
+    // (an e4m3 pool input, ResNet50 fp8: pooled from e4m3 in the head, C >= 2048)
+    if (shapes[pool.in].fp8 && shapes[pool.in].C < 2048) return false;
+    return L.fc && !L.fp8 && !L.relu && L.cin == shapes[pool.in].C && head_supported(L.cin, L.cout, L.kpad, L.npad);
+  }
+
+  // ops[oi] is the last conv (stream path, whole-image workgroups) and
+  // ops[oi+1] the global average pool, the only reader of its output: the
+  // conv's epilogue writes the pooled bf16 vectors straight into the pool's
+  // output activation (and, under a graph, skips storing its own).
+  bool pool_fusable(size_t oi) const {
+    if (!opt.fused_pool || oi + 1 >= ops.size()) return false;
+    const Op& c = ops[oi];
+    const Op& p = ops[oi + 1];
+    if (p.type != OpType::AvgPoolGlobal || p.in != c.out) return false;
+    if (shapes[p.out].fp8 || shapes[p.out].f32 || shapes[p.in].fp8 || !only_reader(c.out, oi + 1)) return false;
+    const ConvLayer& L = convs[c.conv];
+    const ActShape& is = shapes[c.in];
+    return !L.fp8 && path[oi] == Path::Stream && conv3x3_stream_pool_supported(is.H, is.W, is.C, L.cout, L.stride);
+  }
+
+  // ops[oi] is a block's downsample (1x1/s2, BN, no ReLU) and ops[oi+1] the
+  // block's 3x3/s2 conv1 on the same input, run by the stream conv (or the
+  // query-batch conv, which needs the downsample's fragment-order weights).
+  bool ds_fusable(size_t oi) const {
+    if (!conv(oi + 1)) return false;
+    const Op& d = ops[oi];
+    const Op& c = ops[oi + 1];
+    const ConvLayer& D = convs[d.conv];
+    const ConvLayer& L = convs[c.conv];
+    return d.in == c.in && D.plain_ds2() && !D.relu && d.res < 0 && D.cout == L.cout && L.stride == 2 &&
+           !shapes[d.out].fp8 && !shapes[d.out].f32 &&
+           (path[oi + 1] == Path::Stream || (path[oi + 1] == Path::Small && D.wf_off));
+  }
+
+  // ops[oi], ops[oi+1] = conv1 (+ReLU) and conv2 (+identity residual, ReLU) of
+  // a 56x56x64 basic block, both on the register-weight row conv, and conv1's
+  // output read by nothing else: conv3x3_block runs the pair with the
+  // intermediate kept in LDS (not written to its activation).
+  // One workgroup per image walks all 56 rows (~100 us per round of num_cus
+  // images at B=256 vs ~2 x 72 us for the two row convs, which split images
+  // into strips; B=1: 86 us fused vs ~30 us as strips;
+  // profiles/r2_block_kernel_stats.txt).
+  bool block_fusable(size_t oi) const {
+    if (!opt.fused_block || !opt.rows_wreg || !full_rounds() || !conv(oi + 1)) return false;
+    const Op& c1 = ops[oi];
+    const Op& c2 = ops[oi + 1];
+    if (c2.in != c1.out || c1.res >= 0 || c2.res != c1.in || c1.side || c2.side || !only_reader(c1.out, oi + 1))
+      return false;
+    const ConvLayer& L1 = convs[c1.conv];
+    const ConvLayer& L2 = convs[c2.conv];
+    const ActShape& is = shapes[c1.in];
+    return L1.relu && L2.relu && L1.wf_off && L2.wf_off && conv3x3_block_supported(is.H, is.W, is.C) &&
+           L1.cout == is.C && L2.cout == is.C && !shapes[c1.in].fp8 && !shapes[c2.out].fp8 &&
+           path[oi] == Path::Rows && path[oi + 1] == Path::Rows;
+  }
+
+  // a layer1 bottleneck's 3x3 (64 -> 64 on 56x56, fragment-order weights), as bottleneck56.hip runs it
+  static bool bottleneck_conv2(const ConvLayer& L2) {
+    return L2.kh == 3 && L2.kw == 3 && L2.stride == 1 && L2.pad == 1 && L2.relu && L2.cout == 64 && L2.wf_off &&
+           L2.kpad == 576;
+  }
+
+  // ops[oi..oi+2] = conv1 (1x1 256 -> 64, e4m3 in) + conv2 (3x3 64 -> 64) +
+  // conv3 (1x1 64 -> 256 + the block input as residual, e4m3 out) of a
+  // resnet50_fp8 layer1 identity block, the intermediates read by nothing else.
+  bool bottleneck_fusable(size_t oi) const {
+    if (!opt.fused_bottleneck || !e.fp8_ || !conv(oi + 1) || !conv(oi + 2)) return false;
+    const Op& c1 = ops[oi];
+    const Op& c2 = ops[oi + 1];
+    const Op& c3 = ops[oi + 2];
+    if (c1.side || c2.side || c3.side || c2.in != c1.out || c3.in != c2.out || c1.res >= 0 || c2.res >= 0 ||
+        c3.res != c1.in)
+      return false;
+    const ConvLayer& L1 = convs[c1.conv];
+    const ConvLayer& L3 = convs[c3.conv];
+    const ActShape& xs = shapes[c1.in];
+    if (!xs.fp8 || !shapes[c3.out].fp8 || shapes[c1.out].fp8 || shapes[c2.out].fp8) return false;
+    if (!bottleneck56_supported(xs.H, xs.W, xs.C, L1.cout) || !L1.fp8 || L1.kh != 1 || L1.stride != 1 || !L1.relu ||
+        L1.kpad != 256 || L1.npad != 64)
+      return false;
+    if (!bottleneck_conv2(convs[c2.conv]) || !e.bottleneck_conv3(L3) || !L3.wf_off || !L3.relu) return false;
+    return only_reader(c1.out, oi + 1) && only_reader(c2.out, oi + 2);
+  }
+
+  // ops[oi], ops[oi+1] = layer1.0's reduce 1x1 (64 -> 64) + 3x3 -> bottleneck56_head
+  bool bottleneck_head_fusable(size_t oi) const {
+    if (!opt.fused_bottleneck || !conv(oi + 1)) return false;
+    const Op& c1 = ops[oi];
+    const Op& c2 = ops[oi + 1];
+    if (c1.side || c2.side || c2.in != c1.out || c1.res >= 0 || c2.res >= 0) return false;
+    const ConvLayer& L1 = convs[c1.conv];
+    const ConvLayer& L2 = convs[c2.conv];
+    const ActShape& xs = shapes[c1.in];
+    if (xs.fp8 || xs.f32 || shapes[c1.out].fp8 || shapes[c2.out].fp8 || shapes[c2.out].f32) return false;
+    if (!bottleneck56_supported(xs.H, xs.W, 256, 64) || xs.C != 64) return false;
+    if (L1.fc || L1.fp8 || L1.pair || L1.stem_pool || L1.kh != 1 || L1.kw != 1 || L1.stride != 1 || !L1.relu ||
+        L1.cout != 64 || L1.kpad != 64 || L1.npad != 64)
+      return false;
+    return !L2.fp8 && bottleneck_conv2(L2) && only_reader(c1.out, oi + 1);
+  }
+
+  // ops[oi] (with its downsample D left to it: fuse_ds) is layer2.0's conv1 on
+  // the 56x56x64 -> 128 shape: conv3x3_s2rows runs one workgroup per image
+  // (59 us at B=256 vs 72 us for the stream conv's 4 rounds of strips,
+  // profiles/r2_s2rows.txt).
+  bool s2rows_ok(const Op& op, const ConvLayer& D) const {
+    const ConvLayer& L = convs[op.conv];
+    const ActShape& is = shapes[op.in];
+    return opt.s2rows && op.res < 0 && L.wf_off && D.wf_off && full_rounds() &&
+           conv3x3_s2rows_supported(is.H, is.W, is.C, L.cout);
+  }
+
+  // ... and ops[oi - 1] its downsample: the block's conv2 (ops[oi + 1], on
+  // conv3x3_rows28) can compute that downsample as 2 more K steps when it is
+  // the downsample output's only reader (ds_into_conv2).
+  bool ds_conv2_ok(size_t oi) const {
+    if (!opt.ds_into_conv2 || oi < 1 || !conv(oi + 1)) return false;
+    const Op& d = ops[oi - 1];
+    const Op& c2 = ops[oi + 1];
+    if (c2.res != d.out || c2.in != ops[oi].out) return false;
+    const ConvLayer& L2 = convs[c2.conv];
+    const ConvLayer& D = convs[d.conv];
+    if (!L2.wf_off || !D.wf_off || L2.fp8 || shapes[c2.out].fp8 || path[oi + 1] != Path::Rows28) return false;
+    const ActShape& xs = shapes[d.in];
+    if (xs.H != 56 || xs.W != 56 || xs.C != 64 || xs.fp8 || xs.f32 || L2.cout != 128 || D.cout != 128) return false;
+    return only_reader(d.out, oi + 1);
+  }
+
+  // ops[oi] is a bottleneck's expand conv (1x1, residual) and ops[oi + 1] the
+  // next bottleneck's reduce conv on its output, both on conv1x1.hip, in a form
+  // conv1x1_chain runs as one launch (ResNet50 e4m3 layer2.0-2.2 -> 2.1-2.3).
+  // The expand output keeps its other reader (the next expand's residual).
+  bool chain_ok(size_t oi) const {
+    if (!opt.chain_1x1 || !conv(oi + 1)) return false;
+    const Op& x = ops[oi];
+    const Op& r = ops[oi + 1];
+    if (x.res < 0 || r.in != x.out || r.res >= 0 || x.side || r.side) return false;
+    if (path[oi] != Path::OneByOne || path[oi + 1] != Path::OneByOne) return false;
+    if (convs[x.conv].cat_off) return false;  // (an expand with its downsample as a second K block)
+    ConvArgs a = e.conv_geom(x, B), ra = e.conv_geom(r, B);
+    a.split_k = ra.split_k = 1;
+    return conv1x1_chain_supported(a, ra);
+  }
+
+  // AlexNet: the 3x3/s2 max-pool ops[oi + 1] (to out x out) in conv ops[oi]'s
+  // epilogue, when the pool is the conv output's only reader
+  bool maxpool_fusable(size_t oi, int out) const {
+    if (!opt.fused_pool || oi + 1 >= ops.size()) return false;
+    const Op& mp = ops[oi + 1];
+    return mp.type == OpType::MaxPool && mp.in == ops[oi].out && mp.k == 3 && mp.stride == 2 && mp.pad == 0 &&
+           shapes[mp.out].H == out && shapes[mp.out].W == out && only_reader(ops[oi].out, oi + 1);
+  }
+
+  Step& emit(Kernel k, size_t first, int n) {
+    Step st;
+    st.kernel = k;
+    st.first_op = (int)first;
+    st.n_ops = n;
+    steps.push_back(st);
+    return steps.back();
+  }
+
+  void plan_conv(size_t oi, bool side_ready, bool keep_acts) {
+    const Op& op = ops[oi];
+    const ConvLayer& L = convs[op.conv];
+    const ActShape& is = shapes[op.in];
+    if (cat_by[oi] >= 0) {  // computed by its expand conv (conv1x1 x2)
+      emit(Kernel::None, oi, 1);
+      return;
+    }
+    if (opt.fuse_ds && op.side && ds_fusable(oi)) {  // computed by the next op (the block's stride-2 conv1)
+      skip_ds = (int)oi;
+      emit(Kernel::None, oi, 1);
+      return;
+    }
+    // A downsample conv may run on the side stream, concurrently with its
+    // block's conv1 (both read the block input; conv2 joins them through the
+    // residual). The fused multi-op kernels stay on the main stream.
+    const bool side = side_ready && op.side;
+    // query-sized batches: weight-streaming GEMV (AlexNet classifier)
+    if (L.fc && !L.fp8 && !shapes[op.out].fp8 && opt.fc_small && fc_small_supported(B, L.cin, L.cin, L.kpad)) {
+      emit(Kernel::FcSmall, oi, 1).side = side;
+      return;
+    }
+    if (L.cat_off && op.res >= 0 && cat_ds[oi] >= 0) {  // expand conv + its stride-1 downsample as one K-concatenated GEMM
+      Step& st = emit(Kernel::Conv1x1Cat, oi, 1);
+      st.ds_op = cat_ds[oi];
+      st.side = side;
+      return;
+    }
+    if (!side) {
+      if (chain_ok(oi)) return (void)emit(Kernel::Conv1x1Chain, oi, 2);
+      if (bottleneck_fusable(oi)) return (void)emit(Kernel::Bottleneck56, oi, 3);
+      if (bottleneck_head_fusable(oi)) return (void)emit(Kernel::Bottleneck56Head, oi, 2);
+      if (block_fusable(oi)) return (void)emit(Kernel::Block, oi, 2);
+    }
+    Step& st = emit(Kernel::Igemm, oi, 1);
+    st.side = side;
+    const int ds = (skip_ds >= 0 && skip_ds + 1 == (int)oi) ? skip_ds : -1;  // its block's downsample, left to it
+    const ConvLayer* D = ds >= 0 ? &convs[ops[ds].conv] : nullptr;
+    switch (path[oi]) {
+      case Path::Stream: {
+        if (D && s2rows_ok(op, *D)) {
+          st.kernel = Kernel::S2Rows;
+          if (ds_conv2_ok(oi))
+            ds_conv2 = ds;  // the downsample runs inside conv2
+          else
+            st.ds_op = ds;
           break;
         }
-        // images already SxS feed the fused stem directly (stem_conv_pool_u8)
-        if (paired && opt_.fused_preprocess && Hin == image_size_ && Win == image_size_) break;
+        // ResNet50 layer2.0.conv2: one weight-stationary workgroup per image
+        if (!D && opt.s2rows128 && op.res < 0 && L.wf_off && L.stride == 2 && full_rounds() &&
+            conv3x3_s2rows128_supported(is.H, is.W, is.C, L.cout)) {
+          st.kernel = Kernel::S2Rows128;
+          break;
+        }
+        st.kernel = Kernel::Stream;
+        st.ds_op = ds;
+        // (wf_off may exist for conv3x3_s2rows alone)
+        st.wreg = L.wf_off && opt.stream_wreg && (!D || D->wf_off) &&
+                  conv3x3_stream_uses_frag(is.H, is.W, is.C, L.cout, L.stride);
+        pooled = !side && pool_fusable(oi);
+        if (pooled) {
+          st.pool_op = (int)oi + 1;
+          st.store_y = keep_acts;  // eager / profile runs keep the activation (tests read it)
+        }
+        break;
+      }
+      case Path::Direct13:  // AlexNet features.10 + features.12
+        st.kernel = Kernel::Direct13;
+        if (!side && L.relu && conv3x3_13_pool_supported(is.C, L.cout) && maxpool_fusable(oi, 6)) {
+          st.pool_op = (int)oi + 1;
+          st.n_ops = 2;
+        }
+        break;
+      case Path::Direct27:  // AlexNet features.3 + features.5
+        st.kernel = Kernel::Direct27;
+        if (!side && maxpool_fusable(oi, 13)) {
+          st.pool_op = (int)oi + 1;
+          st.n_ops = 2;
+        }
+        break;
+      case Path::Small:
+        st.kernel = Kernel::Small;
+        st.ds_op = ds;
+        st.count = conv_small_pick_mf(B, is.H, is.W, is.C, L.cout, L.stride, cus);
+        break;
+      case Path::Stream8:
+        st.kernel = Kernel::Stream8;
+        break;
+      case Path::Rows28:
+        st.kernel = Kernel::Rows28;
+        if (ds_conv2 >= 0 && op.res == ops[ds_conv2].out) {
+          st.ds_op = ds_conv2;
+          ds_conv2 = -1;
+        }
+        break;
+      case Path::Rows:
+        st.kernel = Kernel::Rows;
+        st.wreg = L.wf_off && opt.rows_wreg;
+        st.count = conv3x3_rows_pick_strip(B, is.H, st.wreg ? 2 * cus : cus);
+        break;
+      case Path::OneByOne:
+        st.kernel = Kernel::Conv1x1;
+        break;
+      case Path::BigTile: {
+        const ConvArgs a = e.conv_geom(op, B);
+        st.kernel = Kernel::BigTile;
+        st.cfg = conv_bigtile_pick(a, cus);
+        st.count = conv_bigtile_splits(a, st.cfg, cus);  // (run_ops: 1 if the reserved slab is too small)
+        break;
+      }
+      case Path::Igemm:
+        break;
+      case Path::Fc: {
+        if (side) break;  // (its partials need the main stream's split-K workspace): the implicit GEMM
+        const ConvArgs a = e.conv_geom(op, B);
+        st.kernel = Kernel::FcGemm;
+        st.count = fc_gemm_splits(a, cus);
+        while (st.count > 1 && ((size_t)st.count * B * a.Npad > kSplitKWsElems || (a.Kpad / 64) % st.count))
+          --st.count;
+        break;
+      }
+    }
+  }
+
+  std::vector<Step> run(bool native, bool side, bool keep_acts) {
+    // never a side stream next to a big-tile conv
+    const bool side_ready = side && std::find(path.begin(), path.end(), Path::BigTile) == path.end();
+    for (size_t oi = 0; oi < ops.size(); oi = steps.back().first_op + steps.back().n_ops) {
+      const Op& op = ops[oi];
+      switch (op.type) {
+        case OpType::Preprocess:
+          // AlexNet: 224x224 u8 images -> features.2's output in one kernel
+          if (native && opt.fused_preprocess && conv(oi + 1) && oi + 2 < ops.size() &&
+              ops[oi + 2].type == OpType::MaxPool && convs[ops[oi + 1].conv].alex_stem)
+            emit(Kernel::AlexStem, oi, 3);
+          // images already SxS feed the fused stem directly (StemPoolU8)
+          else if (native && opt.fused_preprocess && op.k == 1)
+            emit(Kernel::None, oi, 1);
+          else
+            emit(Kernel::Preprocess, oi, 1);
+          break;
+        case OpType::Conv:
+          plan_conv(oi, side_ready, keep_acts);
+          break;
+        case OpType::StemPool: {
+          const ConvLayer& L = convs[op.conv];
+          const int PH = shapes[op.out].H;
+          if (native && opt.fused_preprocess) {
+            Step& st = emit(Kernel::StemPoolU8, oi, 1);
+            st.count = opt.stem_roles ? stem_pool_u8_pick_strip(B, PH, cus) : stem_pool_pick_strip(B, PH, cus);
+            st.wreg = opt.stem_dense && L.wf_off;
+          } else {
+            emit(Kernel::StemPool, oi, 1).count = stem_pool_pick_strip(B, PH, cus);
+          }
+          break;
+        }
+        case OpType::MaxPool:
+          emit(Kernel::MaxPool, oi, 1);
+          break;
+        case OpType::AvgPoolGlobal:
+          if (pooled) {  // pooled by the last conv's epilogue; fc + softmax / top-1 in one launch, or as ops
+            emit(Kernel::None, oi, 1);
+            if (head_fusable(oi)) emit(Kernel::HeadPooled, oi + 1, 2);
+          } else if (head_fusable(oi) && B >= kPoolThenHeadB) {
+            // throughput batches: pool once, then fc + softmax/top-1 on the
+            // pooled rows (head_fused pools its images again in every class
+            // split: resnet50_fp8 b256 86 us, 8 x 25.7 MB of e4m3 reads)
+            emit(Kernel::AvgPoolGlobal, oi, 1);
+            emit(Kernel::HeadPooled, oi + 1, 2);
+          } else if (head_fusable(oi)) {  // avgpool + fc + softmax/top-1 in one launch
+            emit(Kernel::HeadFused, oi, 3);
+          } else {
+            emit(Kernel::AvgPoolGlobal, oi, 1);
+          }
+          break;
+        case OpType::AvgPoolAdaptive:
+          emit(Kernel::AvgPoolAdaptive, oi, 1);
+          break;
+        case OpType::SoftmaxTop1:
+          emit(Kernel::SoftmaxTop1, oi, 1);
+          break;
+      }
+    }
+    return std::move(steps);
+  }
+};
+
+std::vector<Step> Engine::plan(int B, bool native, bool side, bool keep_acts) const {
+  return Planner(*this, B).run(native, side, keep_acts);
+}
+
+std::string Engine::step_detail(const Step& st) const {
+  std::string d;
+  auto add = [&](const std::string& s) { d += (d.empty() ? "" : " ") + s; };
+  const bool in_k = st.kernel == Kernel::Rows28 || st.kernel == Kernel::Conv1x1Cat;  // no activation written
+  if (st.ds_op >= 0) add((in_k ? "dsk=" : "ds=") + ops_[st.ds_op].name);
+  if (st.pool_op >= 0) add("pool=" + ops_[st.pool_op].name);
+  if (st.wreg) add("wreg");
+  if (!st.store_y) add("nostore");
+  if (st.side) add("side");
+  if (st.cfg >= 0) add("cfg=" + std::to_string(st.cfg));
+  if (st.count > 0) {
+    const char* what = st.kernel == Kernel::Small ? "mf=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm) ? "splits=" : "strip=";
+    add(what + std::to_string(st.count));
+  }
+  return d;
+}
+
+std::vector<Engine::PlanLine> Engine::plan_lines(const std::vector<Step>& steps) const {
+  std::vector<PlanLine> out;
+  for (const Step& st : steps) out.push_back(PlanLine{kernel_name(st.kernel), ops_[st.first_op].name, step_detail(st), st.n_ops});
+  return out;
+}
+
+// ---------------------------------------------------------------- executor
+void Engine::run_ops(const std::vector<Step>& steps, const uint8_t* images, int B, int Hin, int Win, int32_t* idx,
+                     float* prob, float* logits, hipStream_t s, std::vector<hipEvent_t>* evs, bool trace) {
+  size_t ei = 0;
+  if (evs) DMLC_HIP_CHECK(hipEventRecord((*evs)[ei++], s));
+  std::map<int, hipEvent_t> joined;  // activation -> event its side-stream producer recorded
+  const uint8_t* wa = (const uint8_t*)warena_;
+  auto W = [&](size_t off) { return (const void*)(wa + off); };
+  auto F = [&](size_t off) { return (const float*)(wa + off); };
+  // an e4m3 output's epilogue scale (0: bf16 output)
+  auto inv_scale = [&](int act) { return shapes_[act].fp8 ? 1.f / shapes_[act].scale : 0.f; };
+  int32_t* const idx_out = idx ? idx : dummy_idx_;
+  float* const prob_out = prob ? prob : (float*)(dummy_idx_ + max_batch_);
+  for (const Step& st : steps) {
+    const size_t oi = st.first_op;
+    const Op& op = ops_[oi];
+    std::optional<TraceRange> tr;  // per-op host ranges (not inside a graph capture)
+    if (trace && st.kernel != Kernel::None) tr.emplace(op.name.c_str());
+    hipStream_t cs = s;
+    if (st.side) {
+      DMLC_HIP_CHECK(hipEventRecord(fork_evs_[oi], s));
+      DMLC_HIP_CHECK(hipStreamWaitEvent(side_, fork_evs_[oi], 0));
+      cs = side_;
+    }
+    if (st.kernel != Kernel::None && op.res >= 0 && joined.count(op.res)) {
+      DMLC_HIP_CHECK(hipStreamWaitEvent(s, joined[op.res], 0));
+      joined.erase(op.res);
+    }
+    // the step's (first) conv layer, its input shape, and the downsample it computes
+    const ConvLayer* Lp = op.conv >= 0 ? &convs_[op.conv] : nullptr;
+    const ActShape* isp = op.in >= 0 ? &shapes_[op.in] : nullptr;
+    const Op* d = st.ds_op >= 0 ? &ops_[st.ds_op] : nullptr;
+    const ConvLayer* D = d ? &convs_[d->conv] : nullptr;
+    const void* res = op.res >= 0 ? acts_[op.res] : nullptr;
+    void* ypool = st.pool_op >= 0 ? acts_[ops_[st.pool_op].out] : nullptr;
+    switch (st.kernel) {
+      case Kernel::None:
+        break;
+      case Kernel::AlexStem: {
+        const ConvLayer& L = convs_[ops_[oi + 1].conv];
+        alex_stem_u8(images, W(L.wf_off), F(L.b_off), acts_[ops_[oi + 2].out], B, s);
+        break;
+      }
+      case Kernel::Preprocess: {
+        const bool paired = op.k == 1;
         const int Wr = paired ? 2 * shapes_[op.out].W : shapes_[op.out].W;
         preprocess_u8(images, acts_[op.out], B, Hin, Win, image_size_, op.pad, Wr, s, paired);
         break;
       }
-      case OpType::Conv: {
-        const ConvLayer& L = convs_[op.conv];
-        const ActShape& is = shapes_[op.in];
-        // A downsample conv runs on the side stream, concurrently with its
-        // block's conv1 (both read the block input; conv2 joins them through
-        // the residual). Never next to a big-tile conv: its split-K slices
-        // spin on each other and need their CUs.
-        if (ds_expand_op(oi) >= 0) break;  // computed by its expand conv (conv1x1 x2)
-        if (opt_.fuse_ds && op.side && ds_fusable(oi, B)) {
-          skip_ds = (int)oi;  // computed by the next op (the block's stride-2 conv1)
-          break;
-        }
-        hipStream_t cs = s;
-        if (side_ready && op.side) {
-          DMLC_HIP_CHECK(hipEventRecord(fork_evs_[oi], s));
-          DMLC_HIP_CHECK(hipStreamWaitEvent(side_, fork_evs_[oi], 0));
-          cs = side_;
-        }
-        if (op.res >= 0 && joined.count(op.res)) {
-          DMLC_HIP_CHECK(hipStreamWaitEvent(s, joined[op.res], 0));
-          joined.erase(op.res);
-        }
-        if (L.fc && !L.fp8 && !shapes_[op.out].fp8 && opt_.fc_small && fc_small_supported(B, L.cin, L.cin, L.kpad)) {
-          // query-sized batches: weight-streaming GEMV (AlexNet classifier)
-          const ActShape& os = shapes_[op.out];
-          fc_small(acts_[op.in], L.cin, (const uint8_t*)warena_ + L.w_off, L.kpad,
-                   (const float*)((const uint8_t*)warena_ + L.b_off),
-                   (os.f32 && logits) ? (void*)logits : acts_[op.out], L.cout, os.f32, B, L.cin, L.cout, L.npad,
-                   L.relu, cs);
-          break;
-        }
-        if (L.cat_off && op.res >= 0) {
-          // expand conv + its stride-1 downsample as one K-concatenated GEMM
-          int ds_op = -1;
-          for (size_t i = 0; i < oi; ++i)
-            if (ops_[i].type == OpType::Conv && ops_[i].conv == L.cat_ds && ds_expand_op(i) == (int)oi) ds_op = (int)i;
-          if (ds_op >= 0) {
-            if (joined.count(op.res)) joined.erase(op.res);
-            ConvArgs a = conv_args(op, B, logits);
-            const ConvLayer& D = convs_[L.cat_ds];
-            a.split_k = 1;
-            a.res = nullptr;
-            a.x2 = acts_[ops_[ds_op].in];
-            a.cin2 = D.cin;
-            a.Kpad = L.kpad + D.kpad;
-            a.w = (const uint8_t*)warena_ + L.cat_off;
-            a.bias = (const float*)((const uint8_t*)warena_ + L.cat_b_off);
-            conv1x1(a, num_cus_, cs);
-            break;
-          }
-        }
-        if (cs == s && chain_ok(oi, B)) {
-          ConvArgs a = conv_args(op, B, logits), ra = conv_args(ops_[oi + 1], B, logits);
-          a.split_k = ra.split_k = 1;
-          conv1x1_chain(a, ra, num_cus_, cs);
-          skip = 1;
-          break;
-        }
-        if (cs == s && bottleneck_fusable(oi)) {
-          const ConvLayer& L2 = convs_[ops_[oi + 1].conv];
-          const ConvLayer& L3 = convs_[ops_[oi + 2].conv];
-          const uint8_t* wa = (const uint8_t*)warena_;
-          bottleneck56(acts_[op.in], wa + L.w_off, (const float*)(wa + L.a_off), (const float*)(wa + L.b_off),
-                       wa + L2.wf_off, (const float*)(wa + L2.b_off), wa + L3.wf_off, (const float*)(wa + L3.b_off),
-                       acts_[ops_[oi + 2].out], shapes_[op.in].scale, 1.f / shapes_[ops_[oi + 2].out].scale, B, s);
-          skip = 2;
-          break;
-        }
-        if (cs == s && bottleneck_head_fusable(oi)) {
-          const ConvLayer& L2 = convs_[ops_[oi + 1].conv];
-          const uint8_t* wa = (const uint8_t*)warena_;
-          bottleneck56_head(acts_[op.in], wa + L.w_off, (const float*)(wa + L.b_off), wa + L2.wf_off,
-                            (const float*)(wa + L2.b_off), acts_[ops_[oi + 1].out], B, s);
-          skip = 1;
-          break;
-        }
-        if (cs == s && block_fusable(oi, B)) {
-          const ConvLayer& L2 = convs_[ops_[oi + 1].conv];
-          const uint8_t* wa = (const uint8_t*)warena_;
-          conv3x3_block(acts_[op.in], wa + L.wf_off, (const float*)(wa + L.b_off), wa + L2.wf_off,
-                        (const float*)(wa + L2.b_off), acts_[ops_[oi + 1].out], zero_, B, s);
-          skip = 1;
-          break;
-        }
-        switch (conv_path(op, B)) {
-          case ConvPath::Stream: {
-            const ConvLayer* D = nullptr;
-            int yd = -1;
-            if (skip_ds >= 0 && skip_ds + 1 == (int)oi) {
-              D = &convs_[ops_[skip_ds].conv];
-              yd = ops_[skip_ds].out;
-            }
-            // the fused avgpool keeps the activation for eager/profile runs
-            // (tests read it) and drops it under graph capture
-            const bool fpool = cs == s && pool_fusable(oi, B);
-            if (D && s2rows_ok(op, *D, B)) {
-              const uint8_t* wa = (const uint8_t*)warena_;
-              if (ds_conv2_ok(oi, B)) {  // the downsample runs inside conv2
-                conv3x3_s2rows(acts_[op.in], wa + L.wf_off, (const float*)(wa + L.b_off), nullptr, nullptr,
-                               acts_[op.out], nullptr, zero_, B, L.relu, cs);
-                ds_conv2 = skip_ds;
-              } else {
-                conv3x3_s2rows(acts_[op.in], wa + L.wf_off, (const float*)(wa + L.b_off), wa + D->wf_off,
-                               (const float*)(wa + D->b_off), acts_[op.out], acts_[yd], zero_, B, L.relu, cs);
-              }
-              skip_ds = -1;
-              break;
-            }
-            if (!D && opt_.s2rows128 && op.res < 0 && L.wf_off && L.stride == 2 &&
-                10 * B >= 7 * ((B + num_cus_ - 1) / num_cus_) * num_cus_ &&
-                conv3x3_s2rows128_supported(is.H, is.W, is.C, L.cout)) {
-              const uint8_t* wa = (const uint8_t*)warena_;
-              conv3x3_s2rows128(acts_[op.in], wa + L.wf_off, (const float*)(wa + L.b_off), acts_[op.out], B, L.relu,
-                                shapes_[op.out].fp8 ? 1.f / shapes_[op.out].scale : 0.f, cs);
-              skip_ds = -1;
-              break;
-            }
-            // (wf_off may exist for conv3x3_s2rows alone)
-            const bool wreg = L.wf_off && opt_.stream_wreg && (!D || D->wf_off) &&
-                              conv3x3_stream_uses_frag(is.H, is.W, is.C, L.cout, L.stride);
-            conv3x3_stream(acts_[op.in], (const uint8_t*)warena_ + L.w_off,
-                           (const float*)((const uint8_t*)warena_ + L.b_off), op.res >= 0 ? acts_[op.res] : nullptr,
-                           acts_[op.out], zero_, B, is.H, is.W, is.C, L.cout, L.stride, L.relu, cs, nullptr,
-                           D ? (const uint8_t*)warena_ + D->w_off : nullptr,
-                           D ? (const float*)((const uint8_t*)warena_ + D->b_off) : nullptr,
-                           D ? acts_[yd] : nullptr, wreg ? (const uint8_t*)warena_ + L.wf_off : nullptr,
-                           (wreg && D) ? (const uint8_t*)warena_ + D->wf_off : nullptr,
-                           fpool ? acts_[ops_[oi + 1].out] : nullptr, !fpool || trace || evs,
-                           shapes_[op.out].fp8 ? 1.f / shapes_[op.out].scale : 0.f);
-            pooled = fpool;
-            skip_ds = -1;
-            break;
-          }
-          case ConvPath::Direct13: {
-            // AlexNet features.10 + features.12: the 3x3/s2 max-pool in the
-            // conv's epilogue when the pool is the conv output's only reader
-            void* ypool = nullptr;
-            if (opt_.fused_pool && cs == s && oi + 1 < ops_.size() && L.relu &&
-                conv3x3_13_pool_supported(is.C, L.cout)) {
-              const Op& mp = ops_[oi + 1];
-              bool only = mp.type == OpType::MaxPool && mp.in == op.out && mp.k == 3 && mp.stride == 2 &&
-                          mp.pad == 0 && shapes_[mp.out].H == 6 && shapes_[mp.out].W == 6;
-              for (size_t j = 0; only && j < ops_.size(); ++j)
-                if (j != oi + 1 && (ops_[j].in == op.out || ops_[j].res == op.out)) only = false;
-              if (only) {
-                ypool = acts_[mp.out];
-                skip = 1;
-              }
-            }
-            conv3x3_13(acts_[op.in], (const uint8_t*)warena_ + L.wf_off,
-                       (const float*)((const uint8_t*)warena_ + L.b_off), acts_[op.out], zero_, B, is.C, L.cout,
-                       L.relu, cs, ypool);
-            break;
-          }
-          case ConvPath::Direct27: {
-            // AlexNet features.3 + features.5: the max-pool in the conv's epilogue
-            void* ypool = nullptr;
-            if (opt_.fused_pool && cs == s && oi + 1 < ops_.size()) {
-              const Op& mp = ops_[oi + 1];
-              bool only = mp.type == OpType::MaxPool && mp.in == op.out && mp.k == 3 && mp.stride == 2 &&
-                          mp.pad == 0 && shapes_[mp.out].H == 13 && shapes_[mp.out].W == 13;
-              for (size_t j = 0; only && j < ops_.size(); ++j)
-                if (j != oi + 1 && (ops_[j].in == op.out || ops_[j].res == op.out)) only = false;
-              if (only) {
-                ypool = acts_[mp.out];
-                skip = 1;
-              }
-            }
-            conv5x5_27(acts_[op.in], (const uint8_t*)warena_ + L.wf_off,
-                       (const float*)((const uint8_t*)warena_ + L.b_off), acts_[op.out], zero_, B, cs, ypool);
-            break;
-          }
-          case ConvPath::Small: {
-            const uint8_t* wa = (const uint8_t*)warena_;
-            const ConvLayer* D = nullptr;
-            int yd = -1;
-            if (skip_ds >= 0 && skip_ds + 1 == (int)oi) {
-              D = &convs_[ops_[skip_ds].conv];
-              yd = ops_[skip_ds].out;
-            }
-            conv_small(acts_[op.in], wa + L.wf_off, (const float*)(wa + L.b_off), op.res >= 0 ? acts_[op.res] : nullptr,
-                       acts_[op.out], B, is.H, is.W, is.C, L.cout, L.stride, L.relu,
-                       conv_small_pick_mf(B, is.H, is.W, is.C, L.cout, L.stride, num_cus_), cs,
-                       D ? wa + D->wf_off : nullptr, D ? (const float*)(wa + D->b_off) : nullptr,
-                       D ? acts_[yd] : nullptr);
-            skip_ds = -1;
-            break;
-          }
-          case ConvPath::Stream8: {
-            const uint8_t* wa = (const uint8_t*)warena_;
-            conv3x3_stream8(acts_[op.in], wa + L.wf_off, (const float*)(wa + L.a_off), (const float*)(wa + L.b_off),
-                            acts_[op.out], zero_, B, is.H, is.W, is.C, L.cout, L.stride, L.relu,
-                            1.f / shapes_[op.out].scale, cs);
-            break;
-          }
-          case ConvPath::Rows28:
-            if (ds_conv2 >= 0 && op.res == ops_[ds_conv2].out) {
-              const ConvLayer& D = convs_[ops_[ds_conv2].conv];
-              const uint8_t* wa = (const uint8_t*)warena_;
-              conv3x3_rows28(acts_[op.in], wa + L.wf_off, (const float*)(wa + L.b_off), nullptr, acts_[op.out], B,
-                             L.relu, cs, 0.f, acts_[ops_[ds_conv2].in], wa + D.wf_off,
-                             (const float*)(wa + D.b_off));
-              ds_conv2 = -1;
-              break;
-            }
-            conv3x3_rows28(acts_[op.in], (const uint8_t*)warena_ + L.wf_off,
-                           (const float*)((const uint8_t*)warena_ + L.b_off), op.res >= 0 ? acts_[op.res] : nullptr,
-                           acts_[op.out], B, L.relu, cs, shapes_[op.out].fp8 ? 1.f / shapes_[op.out].scale : 0.f);
-            break;
-          case ConvPath::Rows:
-            conv3x3_rows(acts_[op.in], (const uint8_t*)warena_ + L.w_off,
-                         (const float*)((const uint8_t*)warena_ + L.b_off), op.res >= 0 ? acts_[op.res] : nullptr,
-                         acts_[op.out], zero_, B, is.H, is.W, is.C, L.relu,
-                         conv3x3_rows_pick_strip(B, is.H, (L.wf_off && opt_.rows_wreg) ? 2 * num_cus_ : num_cus_),
-                         cs,
-                         (L.wf_off && opt_.rows_wreg) ? (const uint8_t*)warena_ + L.wf_off : nullptr);
-            break;
-          case ConvPath::OneByOne: {
-            ConvArgs a = conv_args(op, B, logits);
-            a.split_k = 1;
-            conv1x1(a, num_cus_, cs);
-            break;
-          }
-          case ConvPath::BigTile: {
-            const ConvArgs a = conv_args(op, B, logits);
-            const int bt = conv_bigtile_pick(a, num_cus_);
-            int splits = conv_bigtile_splits(a, bt, num_cus_);
-            if (conv_bigtile_ws_bytes(conv_bigtile_slabs(a, bt, splits)) > bt_ws_bytes_) splits = 1;
-            conv2d_bigtile(a, bt, splits, bt_ws_, bt_ws_bytes_, cs);
-            break;
-          }
-          case ConvPath::Igemm: {
-            ConvArgs a = conv_args(op, B, logits);
-            if (cs != s) a.split_k = 1;  // the split-K workspace belongs to the main stream
-            conv2d_igemm(a, cs);
-            break;
-          }
-          case ConvPath::Fc: {
-            ConvArgs a = conv_args(op, B, logits);
-            if (cs != s) {  // (its partials need the main stream's split-K workspace)
-              a.split_k = 1;
-              conv2d_igemm(a, cs);
-              break;
-            }
-            int sp = fc_gemm_splits(a, num_cus_);
-            while (sp > 1 && ((size_t)sp * B * a.Npad > ws_elems_ || (a.Kpad / 64) % sp)) --sp;
-            a.ws = ws_;
-            fc_gemm(a, sp, cs);
-            break;
-          }
-        }
-        if (cs != s) {
-          DMLC_HIP_CHECK(hipEventRecord(join_evs_[oi], side_));
-          joined[op.out] = join_evs_[oi];
-        }
+      case Kernel::StemPoolU8:
+        stem_conv_pool_u8(images, W(Lp->w_off), F(Lp->b_off), acts_[op.out], B, image_size_, st.count, s,
+                          st.wreg ? W(Lp->wf_off) : nullptr);
+        break;
+      case Kernel::StemPool:
+        stem_conv_pool(acts_[op.in], W(Lp->w_off), F(Lp->b_off), acts_[op.out], B, image_size_, isp->W, st.count, s);
+        break;
+      case Kernel::FcSmall: {
+        const ConvLayer& L = *Lp;
+        const ActShape& os = shapes_[op.out];
+        fc_small(acts_[op.in], L.cin, W(L.w_off), L.kpad, F(L.b_off), (os.f32 && logits) ? (void*)logits : acts_[op.out],
+                 L.cout, os.f32, B, L.cin, L.cout, L.npad, L.relu, cs);
         break;
       }
-      case OpType::StemPool: {
-        const ConvLayer& L = convs_[op.conv];
-        if (opt_.fused_preprocess && Hin == image_size_ && Win == image_size_) {
-          stem_conv_pool_u8(images, (const uint8_t*)warena_ + L.w_off,
-                            (const float*)((const uint8_t*)warena_ + L.b_off), acts_[op.out], B, image_size_,
-                            opt_.stem_roles ? stem_pool_u8_pick_strip(B, shapes_[op.out].H, num_cus_)
-                                            : stem_pool_pick_strip(B, shapes_[op.out].H, num_cus_),
-                            s, opt_.stem_dense && L.wf_off ? (const uint8_t*)warena_ + L.wf_off : nullptr);
-          break;
-        }
-        stem_conv_pool(acts_[op.in], (const uint8_t*)warena_ + L.w_off,
-                       (const float*)((const uint8_t*)warena_ + L.b_off), acts_[op.out], B, image_size_,
-                       shapes_[op.in].W, stem_pool_pick_strip(B, shapes_[op.out].H, num_cus_), s);
+      case Kernel::Conv1x1Cat: {
+        ConvArgs a = conv_geom(op, B);
+        bind(a, op, logits);
+        a.split_k = 1;
+        a.res = nullptr;
+        a.x2 = acts_[d->in];
+        a.cin2 = D->cin;
+        a.Kpad = Lp->kpad + D->kpad;
+        a.w = W(Lp->cat_off);
+        a.bias = F(Lp->cat_b_off);
+        conv1x1(a, num_cus_, cs);
         break;
       }
-      case OpType::MaxPool: {
-        const ActShape& i = shapes_[op.in];
+      case Kernel::Conv1x1Chain: {
+        ConvArgs a = conv_geom(op, B), ra = conv_geom(ops_[oi + 1], B);
+        bind(a, op, logits);
+        bind(ra, ops_[oi + 1], logits);
+        a.split_k = ra.split_k = 1;
+        conv1x1_chain(a, ra, num_cus_, cs);
+        break;
+      }
+      case Kernel::Bottleneck56: {
+        const ConvLayer& L = *Lp;
+        const ConvLayer& L2 = convs_[ops_[oi + 1].conv];
+        const ConvLayer& L3 = convs_[ops_[oi + 2].conv];
+        const int y = ops_[oi + 2].out;
+        bottleneck56(acts_[op.in], W(L.w_off), F(L.a_off), F(L.b_off), W(L2.wf_off), F(L2.b_off), W(L3.wf_off),
+                     F(L3.b_off), acts_[y], isp->scale, 1.f / shapes_[y].scale, B, s);
+        break;
+      }
+      case Kernel::Bottleneck56Head: {
+        const ConvLayer& L2 = convs_[ops_[oi + 1].conv];
+        bottleneck56_head(acts_[op.in], W(Lp->w_off), F(Lp->b_off), W(L2.wf_off), F(L2.b_off), acts_[ops_[oi + 1].out],
+                          B, s);
+        break;
+      }
+      case Kernel::Block: {
+        const ConvLayer& L2 = convs_[ops_[oi + 1].conv];
+        conv3x3_block(acts_[op.in], W(Lp->wf_off), F(Lp->b_off), W(L2.wf_off), F(L2.b_off), acts_[ops_[oi + 1].out],
+                      zero_, B, s);
+        break;
+      }
+      case Kernel::S2Rows:  // without ds_op the downsample runs inside conv2 (Rows28)
+        conv3x3_s2rows(acts_[op.in], W(Lp->wf_off), F(Lp->b_off), D ? W(D->wf_off) : nullptr,
+                       D ? F(D->b_off) : nullptr, acts_[op.out], D ? acts_[d->out] : nullptr, zero_, B, Lp->relu, cs);
+        break;
+      case Kernel::S2Rows128:
+        conv3x3_s2rows128(acts_[op.in], W(Lp->wf_off), F(Lp->b_off), acts_[op.out], B, Lp->relu, inv_scale(op.out), cs);
+        break;
+      case Kernel::Stream: {
+        const ConvLayer& L = *Lp;
+        conv3x3_stream(acts_[op.in], W(L.w_off), F(L.b_off), res, acts_[op.out], zero_, B, isp->H, isp->W, isp->C,
+                       L.cout, L.stride, L.relu, cs, nullptr, D ? W(D->w_off) : nullptr, D ? F(D->b_off) : nullptr,
+                       D ? acts_[d->out] : nullptr, st.wreg ? W(L.wf_off) : nullptr,
+                       (st.wreg && D) ? W(D->wf_off) : nullptr, ypool, st.store_y, inv_scale(op.out));
+        break;
+      }
+      case Kernel::Direct13:
+        conv3x3_13(acts_[op.in], W(Lp->wf_off), F(Lp->b_off), acts_[op.out], zero_, B, isp->C, Lp->cout, Lp->relu, cs,
+                   ypool);
+        break;
+      case Kernel::Direct27:
+        conv5x5_27(acts_[op.in], W(Lp->wf_off), F(Lp->b_off), acts_[op.out], zero_, B, cs, ypool);
+        break;
+      case Kernel::Small:
+        conv_small(acts_[op.in], W(Lp->wf_off), F(Lp->b_off), res, acts_[op.out], B, isp->H, isp->W, isp->C, Lp->cout,
+                   Lp->stride, Lp->relu, st.count, cs, D ? W(D->wf_off) : nullptr, D ? F(D->b_off) : nullptr,
+                   D ? acts_[d->out] : nullptr);
+        break;
+      case Kernel::Stream8:
+        conv3x3_stream8(acts_[op.in], W(Lp->wf_off), F(Lp->a_off), F(Lp->b_off), acts_[op.out], zero_, B, isp->H,
+                        isp->W, isp->C, Lp->cout, Lp->stride, Lp->relu, 1.f / shapes_[op.out].scale, cs);
+        break;
+      case Kernel::Rows28:
+        if (D)  // the block's downsample as 2 more K steps instead of the residual read
+          conv3x3_rows28(acts_[op.in], W(Lp->wf_off), F(Lp->b_off), nullptr, acts_[op.out], B, Lp->relu, cs, 0.f,
+                         acts_[d->in], W(D->wf_off), F(D->b_off));
+        else
+          conv3x3_rows28(acts_[op.in], W(Lp->wf_off), F(Lp->b_off), res, acts_[op.out], B, Lp->relu, cs,
+                         inv_scale(op.out));
+        break;
+      case Kernel::Rows:
+        conv3x3_rows(acts_[op.in], W(Lp->w_off), F(Lp->b_off), res, acts_[op.out], zero_, B, isp->H, isp->W, isp->C,
+                     Lp->relu, st.count, cs, st.wreg ? W(Lp->wf_off) : nullptr);
+        break;
+      case Kernel::Conv1x1: {
+        ConvArgs a = conv_geom(op, B);
+        bind(a, op, logits);
+        a.split_k = 1;
+        conv1x1(a, num_cus_, cs);
+        break;
+      }
+      case Kernel::BigTile: {
+        ConvArgs a = conv_geom(op, B);
+        bind(a, op, logits);
+        // (a slab reserved for a smaller max_batch: no K split)
+        const int splits = conv_bigtile_ws_bytes(conv_bigtile_slabs(a, st.cfg, st.count)) > bt_ws_bytes_ ? 1 : st.count;
+        conv2d_bigtile(a, st.cfg, splits, bt_ws_, bt_ws_bytes_, cs);
+        break;
+      }
+      case Kernel::Igemm: {
+        ConvArgs a = conv_geom(op, B);
+        bind(a, op, logits);
+        if (st.side) a.split_k = 1;  // the split-K workspace belongs to the main stream
+        conv2d_igemm(a, cs);
+        break;
+      }
+      case Kernel::FcGemm: {
+        ConvArgs a = conv_geom(op, B);
+        bind(a, op, logits);
+        fc_gemm(a, st.count, cs);
+        break;
+      }
+      case Kernel::MaxPool: {
         const ActShape& o = shapes_[op.out];
-        maxpool2d(acts_[op.in], acts_[op.out], B, i.H, i.W, i.C, o.H, o.W, op.k, op.stride, op.pad, s);
+        maxpool2d(acts_[op.in], acts_[op.out], B, isp->H, isp->W, isp->C, o.H, o.W, op.k, op.stride, op.pad, s);
         break;
       }
-      case OpType::AvgPoolGlobal: {
-        const ActShape& i = shapes_[op.in];
-        if (pooled) {  // pooled by the last conv's epilogue
-          if (head_fusable(oi)) {  // fc + softmax/top-1 in one launch
-            const ConvLayer& L = convs_[ops_[oi + 1].conv];
-            head_pooled(acts_[op.out], (const uint8_t*)warena_ + L.w_off,
-                        (const float*)((const uint8_t*)warena_ + L.b_off), B, i.C, L.cout, L.kpad, L.npad,
-                        logits ? logits : (float*)acts_[ops_[oi + 1].out], idx ? idx : dummy_idx_,
-                        prob ? prob : (float*)(dummy_idx_ + max_batch_), head_ws_, head_ws_bytes_, num_cus_, s);
-            skip = 2;
-          }
-          break;  // else the fc and softmax ops follow
-        }
-        if (head_fusable(oi) && B >= kPoolThenHeadB) {
-          // throughput batches: pool once, then fc + softmax/top-1 on the
-          // pooled rows (head_fused pools its images again in every class
-          // split: resnet50_fp8 b256 86 us, 8 x 25.7 MB of e4m3 reads)
-          const ConvLayer& L = convs_[ops_[oi + 1].conv];
-          avgpool_global(acts_[op.in], acts_[op.out], B, i.H * i.W, i.C, s, i.fp8, i.scale);
-          head_pooled(acts_[op.out], (const uint8_t*)warena_ + L.w_off,
-                      (const float*)((const uint8_t*)warena_ + L.b_off), B, i.C, L.cout, L.kpad, L.npad,
-                      logits ? logits : (float*)acts_[ops_[oi + 1].out], idx ? idx : dummy_idx_,
-                      prob ? prob : (float*)(dummy_idx_ + max_batch_), head_ws_, head_ws_bytes_, num_cus_, s);
-          skip = 2;
-          break;
-        }
-        if (head_fusable(oi)) {  // avgpool + fc + softmax/top-1 in one launch
-          const ConvLayer& L = convs_[ops_[oi + 1].conv];
-          head_fused(acts_[op.in], (const uint8_t*)warena_ + L.w_off,
-                     (const float*)((const uint8_t*)warena_ + L.b_off), B, i.H * i.W, i.C, L.cout, L.kpad, L.npad,
-                     logits ? logits : (float*)acts_[ops_[oi + 1].out], idx ? idx : dummy_idx_,
-                     prob ? prob : (float*)(dummy_idx_ + max_batch_), head_ws_, head_ws_bytes_, num_cus_, s, i.fp8,
-                     i.scale);
-          skip = 2;
-          break;
-        }
-        avgpool_global(acts_[op.in], acts_[op.out], B, i.H * i.W, i.C, s, i.fp8, i.scale);
+      case Kernel::AvgPoolGlobal:
+        avgpool_global(acts_[op.in], acts_[op.out], B, isp->H * isp->W, isp->C, s, isp->fp8, isp->scale);
+        break;
+      case Kernel::HeadPooled:  // op = the fc on the pooled rows, then softmax / top-1
+        head_pooled(acts_[op.in], W(Lp->w_off), F(Lp->b_off), B, Lp->cin, Lp->cout, Lp->kpad, Lp->npad,
+                    logits ? logits : (float*)acts_[op.out], idx_out, prob_out, head_ws_, head_ws_bytes_, num_cus_, s);
+        break;
+      case Kernel::HeadFused: {  // op = the avgpool, then fc and softmax / top-1
+        const ConvLayer& L = convs_[ops_[oi + 1].conv];
+        head_fused(acts_[op.in], W(L.w_off), F(L.b_off), B, isp->H * isp->W, isp->C, L.cout, L.kpad, L.npad,
+                   logits ? logits : (float*)acts_[ops_[oi + 1].out], idx_out, prob_out, head_ws_, head_ws_bytes_,
+                   num_cus_, s, isp->fp8, isp->scale);
         break;
       }
-      case OpType::AvgPoolAdaptive: {
-        const ActShape& i = shapes_[op.in];
+      case Kernel::AvgPoolAdaptive: {
         const ActShape& o = shapes_[op.out];
-        avgpool_adaptive(acts_[op.in], acts_[op.out], B, i.H, i.W, i.C, o.H, o.W, s);
+        avgpool_adaptive(acts_[op.in], acts_[op.out], B, isp->H, isp->W, isp->C, o.H, o.W, s);
         break;
       }
-      case OpType::SoftmaxTop1: {
-        const float* lg = logits ? logits : (const float*)acts_[op.in];
-        softmax_top1(lg, B, num_classes_, num_classes_, idx ? idx : dummy_idx_,
-                     prob ? prob : (float*)(dummy_idx_ + max_batch_), s);
+      case Kernel::SoftmaxTop1:
+        softmax_top1(logits ? logits : (const float*)acts_[op.in], B, num_classes_, num_classes_, idx_out, prob_out, s);
         break;
-      }
     }
-    if (evs) DMLC_HIP_CHECK(hipEventRecord((*evs)[ei++], s));
+    if (st.side) {
+      DMLC_HIP_CHECK(hipEventRecord(join_evs_[oi], side_));
+      joined[op.out] = join_evs_[oi];
+    }
+    for (int i = 0; evs && i < st.n_ops; ++i) DMLC_HIP_CHECK(hipEventRecord((*evs)[ei++], s));
   }
 }
 
@@ -1536,6 +1654,7 @@ void Engine::forward(const uint8_t* images, int B, int Hin, int Win, int32_t* id
   if (B > max_batch_) throw std::invalid_argument("batch exceeds reserved max_batch");
   if (!images) throw std::invalid_argument("null images");
   DMLC_HIP_CHECK(hipSetDevice(device_));
+  const bool native = Hin == image_size_ && Win == image_size_;
   // Forwards share the activation arena: one on a different stream than the
   // previous forward is ordered after it (an event, only then).
   if (last_stream_valid_ && stream != last_stream_) DMLC_HIP_CHECK(hipStreamWaitEvent(stream, ev_out_, 0));
@@ -1547,10 +1666,11 @@ void Engine::forward(const uint8_t* images, int B, int Hin, int Win, int32_t* id
     GraphKey key{images, B, Hin, Win, idx, prob, logits};
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
+      const std::vector<Step> steps = plan(B, native, opt_.fork_ds, false);
       DMLC_HIP_CHECK(hipStreamSynchronize(stream));
       hipGraph_t g;
       DMLC_HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-      run_ops(images, B, Hin, Win, idx, prob, logits, stream_, nullptr, false);
+      run_ops(steps, images, B, Hin, Win, idx, prob, logits, stream_, nullptr, false);
       DMLC_HIP_CHECK(hipStreamEndCapture(stream_, &g));
       hipGraphExec_t ex;
       DMLC_HIP_CHECK(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
@@ -1561,7 +1681,7 @@ void Engine::forward(const uint8_t* images, int B, int Hin, int Win, int32_t* id
     DMLC_HIP_CHECK(hipGraphLaunch(it->second, stream));
   } else {  // eager launches straight onto the caller's stream
     DMLC_TRACE("engine.forward");
-    run_ops(images, B, Hin, Win, idx, prob, logits, stream, nullptr, true);
+    run_ops(plan(B, native, opt_.fork_ds, true), images, B, Hin, Win, idx, prob, logits, stream, nullptr, true);
   }
   DMLC_HIP_CHECK(hipEventRecord(ev_out_, stream));
   last_stream_ = stream;
@@ -1575,7 +1695,9 @@ std::vector<std::pair<std::string, float>> Engine::profile(const uint8_t* images
   DMLC_HIP_CHECK(hipStreamSynchronize(stream));
   std::vector<hipEvent_t> evs(ops_.size() + 1);
   for (auto& e : evs) DMLC_HIP_CHECK(hipEventCreate(&e));
-  run_ops(images, B, Hin, Win, nullptr, nullptr, nullptr, stream_, &evs, true);
+  // per-op event timing keeps every op on one stream
+  run_ops(plan(B, Hin == image_size_ && Win == image_size_, false, true), images, B, Hin, Win, nullptr, nullptr, nullptr,
+          stream_, &evs, true);
   DMLC_HIP_CHECK(hipStreamSynchronize(stream_));
   std::vector<std::pair<std::string, float>> out;
   for (size_t i = 0; i < ops_.size(); ++i) {

@@ -57,6 +57,13 @@ struct ConvLayer {
   // [cout][kpad + ds kpad] bf16 = [W3 | Wd] and bias b3 + bd (0 = none)
   int cat_ds = -1;              // convs_ index of that downsample
   size_t cat_off = 0, cat_b_off = 0;
+
+  // Layer classes shared by the weight layout (who gets a fragment-order
+  // copy at wf_off) and the planner (which kernel may run the layer); `fp8`
+  // is set by the layout pass.
+  bool plain() const { return !fp8 && !fc && !pair && !stem_pool && in_act >= 0; }  // bf16 conv on an NHWC activation
+  bool plain_3x3() const { return plain() && kh == 3 && kw == 3 && pad == 1; }      // plain bf16 3x3/p1 conv
+  bool plain_ds2() const { return plain() && kh == 1 && kw == 1 && stride == 2 && pad == 0; }  // 1x1/s2 downsample
 };
 
 struct Op {
@@ -158,6 +165,37 @@ struct PackRegion {
   size_t off = 0, bytes = 0;
 };
 
+// Split-K workspace of the implicit GEMM and fc_gemm (fp32 elements, 64 MB): a
+// constant, so a host-only engine clamps split_k like one with a device.
+constexpr size_t kSplitKWsElems = (size_t)16 << 20;
+
+// A forward as a list of launches (Engine::plan): which kernel runs which
+// ops, and the few facts the launch needs beyond the ops themselves. Integers,
+// enums and bools only: a plan is made without a device and can be compared.
+// One enumerator per launcher (or form of one) the engine calls.
+enum class Kernel {
+  None,  // nothing to launch: the op is computed inside another step, or not needed
+  AlexStem, StemPoolU8, StemPool, FcSmall, Conv1x1Cat, Conv1x1Chain, Bottleneck56, Bottleneck56Head, Block,
+  S2Rows, S2Rows128, Stream, Stream8, Rows28, Rows, Small, Direct13, Direct27, Conv1x1, BigTile, Igemm, FcGemm,
+  HeadPooled, HeadFused, AvgPoolGlobal, AvgPoolAdaptive, MaxPool, Preprocess, SoftmaxTop1
+};
+const char* kernel_name(Kernel k);
+
+struct Step {
+  Kernel kernel = Kernel::None;
+  int first_op = 0, n_ops = 1;  // ops_[first_op .. first_op + n_ops) are done by this step
+  // a block's downsample op this launch computes: written to its activation
+  // (S2Rows, Stream, Small), or as extra K steps with no activation written
+  // (Rows28: ds_into_conv2, Conv1x1Cat: ds_into_expand)
+  int ds_op = -1;
+  int pool_op = -1;      // pool op whose output the conv's epilogue writes (Stream, Direct13, Direct27)
+  bool wreg = false;     // weights from the layer's wf_off copy (Stream, Rows: register-streamed; StemPoolU8: dense K)
+  bool store_y = true;   // false: the last op's activation is not written (Stream with the pool fused, under a graph)
+  bool side = false;     // runs on the side stream (fork_ds)
+  int cfg = -1;          // BigTile: tile config
+  int count = 0;         // Rows / StemPool / StemPoolU8: strip; Small: mf; BigTile / FcGemm: K splits
+};
+
 class Engine {
  public:
   // arch: resnet18 | resnet34 | resnet50 | alexnet | resnet50_fp8 (layers 2-4
@@ -182,6 +220,32 @@ class Engine {
   static std::vector<PackRegion> pack_audit(const std::string& arch, const WeightMap& weights,
                                             const EngineOptions& options, size_t* total,
                                             int num_classes = 1000, int image_size = 224);
+  // The launches of one forward of B images. native: the images already have
+  // the model's size; side: downsample convs may go to the side stream
+  // (fork_ds; dropped when the plan has a big-tile conv, whose split-K slices
+  // spin on each other and need their CUs); keep_acts: every activation a
+  // test may read is stored (eager / profile runs; a graph capture drops the
+  // last conv's when its pool is fused). Host integer logic only.
+  std::vector<Step> plan(int B, bool native, bool side, bool keep_acts) const;
+  // The plan a graph-captured forward(B, Hin, Win) runs.
+  std::vector<Step> plan(int B, int Hin, int Win) const {
+    return plan(B, Hin == image_size_ && Win == image_size_, opt_.fork_ds, false);
+  }
+  // A step's extra fields as text, e.g. "ds=layer2.0.downsample.0 wreg".
+  std::string step_detail(const Step& st) const;
+  // Host-only like pack_audit (the layout pass runs first: the plan reads
+  // wf_off, cat_off, npad): the plan of a graph-captured native / resized
+  // forward on a device with num_cus compute units, as text. *engine_ops = the
+  // graph's ops.
+  struct PlanLine {
+    std::string kernel, first_op, detail;
+    int n_ops = 1;
+  };
+  static std::vector<PlanLine> plan_audit(const std::string& arch, const WeightMap& weights,
+                                          const EngineOptions& options, int B, bool native, int num_cus,
+                                          std::vector<Op>* engine_ops = nullptr, int num_classes = 1000,
+                                          int image_size = 224);
+  std::vector<PlanLine> plan_lines(const std::vector<Step>& steps) const;
   void* weight_arena() const { return warena_; }
 
   const std::string& arch() const { return arch_; }
@@ -189,6 +253,7 @@ class Engine {
   int num_classes() const { return num_classes_; }
   int image_size() const { return image_size_; }
   int max_batch() const { return max_batch_; }
+  int num_cus() const { return num_cus_; }
   const EngineOptions& options() const { return opt_; }
   hipStream_t stream() const { return stream_; }  // the engine's own (capture) stream
   size_t weight_bytes() const { return weight_bytes_; }
@@ -229,27 +294,23 @@ class Engine {
          const EngineOptions& options);
   void build_graph(const WeightMap& weights, bool calibrate_on_device);
   void pack_weights(const WeightMap& w);
+  void layout_weights();
   std::vector<uint8_t> pack_host(const WeightMap& w, std::vector<PackRegion>* regions);
   void init_device();
   void mark_fp8();
   void calibrate(const WeightMap& w);
-  void run_ops(const uint8_t* images, int B, int Hin, int Win, int32_t* idx, float* prob,
-               float* logits, hipStream_t s, std::vector<hipEvent_t>* evs, bool trace);
-  ConvArgs conv_args(const Op& op, int B, float* logits) const;
-  enum class ConvPath { Stream, Rows, Rows28, Direct13, Direct27, OneByOne, BigTile, Igemm, Small, Stream8, Fc };
-  ConvPath conv_path(const Op& op, int B) const;
-  bool side_safe(int B) const;
-  bool head_fusable(size_t oi) const;
-  bool pool_fusable(size_t oi, int B) const;
-  bool ds_fusable(size_t oi, int B) const;     // ops oi, oi+1 = downsample + stride-2 stream conv1
-  bool block_fusable(size_t oi, int B) const;  // ops oi, oi+1 = a layer1 basic block -> conv3x3_block
-  bool bottleneck_fusable(size_t oi) const;    // ops oi..oi+2 = a layer1 identity bottleneck -> bottleneck56
-  bool bottleneck_head_fusable(size_t oi) const;  // ops oi, oi+1 = layer1.0's reduce + 3x3 -> bottleneck56_head
-  bool bottleneck_conv3(const ConvLayer& L) const;  // L is such a block's expand conv (fragment-order weights)
-  int ds_expand_op(size_t oi) const;  // ops[oi] = a downsample folded into a later expand conv: that op, or -1
-  bool s2rows_ok(const Op& op, const ConvLayer& D, int B) const;  // layer2.0 conv1 + downsample -> conv3x3_s2rows
-  bool ds_conv2_ok(size_t oi, int B) const;
-  bool chain_ok(size_t oi, int B) const;  // ops[oi] (expand) + ops[oi + 1] (reduce) as one conv1x1_chain  // ... and that downsample as K steps of conv2 (ds_into_conv2)
+  // Launch the steps of plan(B, native, ...) in order. evs: an event after
+  // every op (profile); trace: a host trace range per launching op.
+  void run_ops(const std::vector<Step>& steps, const uint8_t* images, int B, int Hin, int Win, int32_t* idx,
+               float* prob, float* logits, hipStream_t s, std::vector<hipEvent_t>* evs, bool trace);
+  // A conv op's launch arguments in two parts: the geometry (shapes, padding,
+  // flags, scales, tile, split-K, persistent grid), which is all the planner
+  // and the kernels' *_supported checks see, and the operands (x, w, bias,
+  // res, y, ws, alpha, zero), which only run_ops binds.
+  ConvArgs conv_geom(const Op& op, int B) const;
+  void bind(ConvArgs& a, const Op& op, float* logits) const;
+  bool bottleneck_conv3(const ConvLayer& L) const;  // L is a fused layer1 bottleneck's expand conv (fragment-order weights)
+  struct Planner;  // kernel choice and fusion for one batch size (engine.cpp)
 
   std::string arch_;
   int device_ = 0;
@@ -275,7 +336,6 @@ class Engine {
   void* bt_ws_ = nullptr;  // big-tile conv split-K hand-off flags + partial-tile slabs
   size_t bt_ws_bytes_ = 0;
   void* zero_ = nullptr;  // 16-B zero page: LDS-DMA source for conv padding taps
-  size_t ws_elems_ = 0;
   int32_t* dummy_idx_ = nullptr;
   void* head_ws_ = nullptr;  // fused head partials + per-group tickets
   size_t head_ws_bytes_ = 0;

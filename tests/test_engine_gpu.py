@@ -629,6 +629,23 @@ def test_unknown_engine_option_is_an_error(gpu):
         InferenceEngine("resnet18", max_batch=1, options={"no_such_path": True})
 
 
+@pytest.mark.parametrize("arch", ["resnet18", "resnet50_fp8"])
+def test_live_plan_matches_host_audit(gpu, arch):
+    """The plan a live engine runs equals the host-only plan_audit for the
+    device's CU count (tests/test_plan_cpu.py pins the audit's sequences), and
+    profile() still reports one entry per op."""
+    from dmlc import native
+    sd = state_dict_f32(build(arch.replace("_fp8", ""), seed=0))
+    eng = InferenceEngine(arch, sd, max_batch=64)
+    weights = {k: v.detach().cpu().float().numpy() for k, v in sd.items()}
+    for B in (4, 64):
+        audit, ops = native().plan_audit(arch, weights, {}, B, True, eng._e.num_cus)
+        assert eng._e.plan(B, 224, 224) == audit, B
+        assert ops == eng._e.op_list()
+    x = torch.zeros(4, 224, 224, 3, dtype=torch.uint8, device=gpu)
+    assert [n for n, _ in eng._e.profile(x.data_ptr(), 4, 224, 224, 0)] == [n for n, _, _, _ in eng._e.op_list()]
+
+
 @pytest.mark.parametrize("B", [64, 256])
 def test_resnet50_fp8_3x3_in_matches_bf16_in(gpu, B):
     """fp8_3x3_in: layer3/4's stride-1 bottleneck 3x3 convs read e4m3 t1
