@@ -396,6 +396,12 @@ PYBIND11_MODULE(_C, m) {
                            uintptr_t stream) {
     softmax_top1(P<float>(logits), B, N, ld, P<int32_t>(idx), P<float>(prob), S(stream));
   });
+  m.attr("MAX_TOPK") = kMaxTopK;
+  m.def("softmax_topk", [](uintptr_t logits, int B, int N, int ld, int k, uintptr_t idx, uintptr_t prob,
+                           uintptr_t stream) {
+    softmax_topk(P<float>(logits), B, N, ld, k, P<int32_t>(idx), P<float>(prob), S(stream));
+  }, py::arg("logits"), py::arg("B"), py::arg("N"), py::arg("ld"), py::arg("k"), py::arg("idx"), py::arg("prob"),
+        py::arg("stream"), py::call_guard<py::gil_scoped_release>());
 
   // ---------------------------------------------------------------- jpeg
   m.def("decode_jpeg", [](py::bytes data) {
@@ -529,13 +535,14 @@ PYBIND11_MODULE(_C, m) {
     return l;
   };
   m.def("plan_audit", [=](const std::string& arch, const py::dict& weights, const std::map<std::string, bool>& options,
-                          int B, bool native, int num_cus, int num_classes, int image_size) {
+                          int B, bool native, int num_cus, int num_classes, int image_size, int topk) {
     std::vector<Op> ops;
     const auto lines = Engine::plan_audit(arch, to_weight_map(weights), engine_options(options), B, native, num_cus,
-                                          &ops, num_classes, image_size);
+                                          &ops, num_classes, image_size, topk);
     return py::make_tuple(plan_list(lines), op_list(ops));
   }, py::arg("arch"), py::arg("weights"), py::arg("options") = std::map<std::string, bool>{}, py::arg("B") = 256,
-     py::arg("native") = true, py::arg("num_cus") = 256, py::arg("num_classes") = 1000, py::arg("image_size") = 224);
+     py::arg("native") = true, py::arg("num_cus") = 256, py::arg("num_classes") = 1000, py::arg("image_size") = 224,
+     py::arg("topk") = 1);
   py::class_<Engine>(m, "Engine")
       .def(py::init([](const std::string& arch, const py::dict& weights, int device, int num_classes,
                        int image_size, const std::map<std::string, bool>& options) {
@@ -562,6 +569,16 @@ PYBIND11_MODULE(_C, m) {
           py::arg("images"), py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("idx"),
           py::arg("prob"), py::arg("logits"), py::arg("stream"), py::arg("use_graph") = true,
           py::call_guard<py::gil_scoped_release>())
+      .def(
+          "forward_topk",
+          [](Engine& e, uintptr_t images, int B, int Hin, int Win, int k, uintptr_t idx, uintptr_t prob,
+             uintptr_t logits, uintptr_t stream, bool use_graph) {
+            e.forward_topk(P<uint8_t>(images), B, Hin, Win, k, P<int32_t>(idx), P<float>(prob), P<float>(logits),
+                           S(stream), use_graph);
+          },
+          py::arg("images"), py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("k"), py::arg("idx"),
+          py::arg("prob"), py::arg("logits"), py::arg("stream"), py::arg("use_graph") = true,
+          py::call_guard<py::gil_scoped_release>())
       .def("profile",
            [](Engine& e, uintptr_t images, int B, int Hin, int Win, uintptr_t stream) {
              return e.profile(P<uint8_t>(images), B, Hin, Win, S(stream));
@@ -573,7 +590,9 @@ PYBIND11_MODULE(_C, m) {
              return py::make_tuple(s.H, s.W, s.C, s.f32);
            })
       .def("op_list", [=](const Engine& e) { return op_list(e.ops()); })
-      .def("plan", [=](const Engine& e, int B, int Hin, int Win) { return plan_list(e.plan_lines(e.plan(B, Hin, Win))); })
+      .def("plan", [=](const Engine& e, int B, int Hin, int Win, int topk) {
+        return plan_list(e.plan_lines(e.plan(B, Hin, Win, topk)));
+      }, py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("topk") = 1)
       .def_property_readonly("num_cus", &Engine::num_cus)
       .def_property_readonly("num_activations", &Engine::num_activations)
       .def_property_readonly("arch", &Engine::arch)

@@ -426,5 +426,12 @@ void fc_small(const void* x, int ldx, const void* w, int ldw, const float* bias,
 // Row-wise softmax + top-1 over fp32 logits [B, ld] (first N columns).
 void softmax_top1(const float* logits, int B, int N, int ld, int32_t* idx, float* prob,
                   hipStream_t s);
+// Row-wise softmax + top-k (softmax_topk.hip): row b of idx / prob holds the
+// classes and softmax probabilities of the k largest of the first N columns,
+// in descending order, equal logits by ascending class. Rank 0 is bit-equal to
+// softmax_top1. 1 <= k <= min(N, kMaxTopK); the logits are assumed finite.
+constexpr int kMaxTopK = 16;
+void softmax_topk(const float* logits, int B, int N, int ld, int k, int32_t* idx /*[B,k]*/, float* prob /*[B,k]*/,
+                  hipStream_t s);
 
 }  // namespace dmlc

@@ -162,12 +162,13 @@ std::vector<PackRegion> Engine::pack_audit(const std::string& arch, const Weight
 
 std::vector<Engine::PlanLine> Engine::plan_audit(const std::string& arch, const WeightMap& weights,
                                                  const EngineOptions& options, int B, bool native, int num_cus,
-                                                 std::vector<Op>* engine_ops, int num_classes, int image_size) {
+                                                 std::vector<Op>* engine_ops, int num_classes, int image_size,
+                                                 int topk) {
   Engine e(HostOnly{}, arch, weights, num_classes, image_size, options);
   e.num_cus_ = num_cus;
   e.layout_weights();
   if (engine_ops) *engine_ops = e.ops_;
-  return e.plan_lines(e.plan(B, native, options.fork_ds, false));
+  return e.plan_lines(e.plan(B, native, options.fork_ds, false, topk));
 }
 
 // Same graph, packing and calibration as `src`, on another device, with an
@@ -929,8 +930,8 @@ const char* kernel_name(Kernel k) {
       "None", "AlexStem", "StemPoolU8", "StemPool", "FcSmall", "Conv1x1Cat", "Conv1x1Chain", "Bottleneck56",
       "Bottleneck56Head", "Block", "S2Rows", "S2Rows128", "Stream", "Stream8", "Rows28", "Rows", "Small", "Direct13",
       "Direct27", "Conv1x1", "BigTile", "Igemm", "FcGemm", "HeadPooled", "HeadFused", "AvgPoolGlobal",
-      "AvgPoolAdaptive", "MaxPool", "Preprocess", "SoftmaxTop1"};
-  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::SoftmaxTop1 + 1, "one name per Kernel");
+      "AvgPoolAdaptive", "MaxPool", "Preprocess", "SoftmaxTop1", "SoftmaxTopK"};
+  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::SoftmaxTopK + 1, "one name per Kernel");
   return names[(size_t)k];
 }
 
@@ -1346,7 +1347,7 @@ struct Engine::Planner {
     }
   }
 
-  std::vector<Step> run(bool native, bool side, bool keep_acts) {
+  std::vector<Step> run(bool native, bool side, bool keep_acts, int topk) {
     // never a side stream next to a big-tile conv
     const bool side_ready = side && std::find(path.begin(), path.end(), Path::BigTile) == path.end();
     for (size_t oi = 0; oi < ops.size(); oi = steps.back().first_op + steps.back().n_ops) {
@@ -1405,12 +1406,20 @@ struct Engine::Planner {
           break;
       }
     }
+    // top-k: the plan above unchanged (its tail still writes the logits and a
+    // top-1 of its own), then the ranking of those logits
+    if (topk > 1) {
+      Step& st = emit(Kernel::SoftmaxTopK, ops.size() - 1, 0);
+      st.count = topk;
+    }
     return std::move(steps);
   }
 };
 
-std::vector<Step> Engine::plan(int B, bool native, bool side, bool keep_acts) const {
-  return Planner(*this, B).run(native, side, keep_acts);
+std::vector<Step> Engine::plan(int B, bool native, bool side, bool keep_acts, int topk) const {
+  if (topk < 1 || topk > std::min(num_classes_, kMaxTopK))
+    throw std::invalid_argument("top-k: k must be in 1..min(num_classes, " + std::to_string(kMaxTopK) + ")");
+  return Planner(*this, B).run(native, side, keep_acts, topk);
 }
 
 std::string Engine::step_detail(const Step& st) const {
@@ -1424,7 +1433,7 @@ std::string Engine::step_detail(const Step& st) const {
   if (st.side) add("side");
   if (st.cfg >= 0) add("cfg=" + std::to_string(st.cfg));
   if (st.count > 0) {
-    const char* what = st.kernel == Kernel::Small ? "mf=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm) ? "splits=" : "strip=";
+    const char* what = st.kernel == Kernel::Small ? "mf=" : st.kernel == Kernel::SoftmaxTopK ? "k=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm) ? "splits=" : "strip=";
     add(what + std::to_string(st.count));
   }
   return d;
@@ -1447,8 +1456,11 @@ void Engine::run_ops(const std::vector<Step>& steps, const uint8_t* images, int 
   auto F = [&](size_t off) { return (const float*)(wa + off); };
   // an e4m3 output's epilogue scale (0: bf16 output)
   auto inv_scale = [&](int act) { return shapes_[act].fp8 ? 1.f / shapes_[act].scale : 0.f; };
-  int32_t* const idx_out = idx ? idx : dummy_idx_;
-  float* const prob_out = prob ? prob : (float*)(dummy_idx_ + max_batch_);
+  // the tail's top-1: the caller's buffers, or scratch when there are none or
+  // when they are the [B, k] outputs of a final SoftmaxTopK step
+  const bool topk = !steps.empty() && steps.back().kernel == Kernel::SoftmaxTopK;
+  int32_t* const idx_out = (idx && !topk) ? idx : dummy_idx_;
+  float* const prob_out = (prob && !topk) ? prob : (float*)(dummy_idx_ + max_batch_);
   for (const Step& st : steps) {
     const size_t oi = st.first_op;
     const Op& op = ops_[oi];
@@ -1639,6 +1651,10 @@ void Engine::run_ops(const std::vector<Step>& steps, const uint8_t* images, int 
       case Kernel::SoftmaxTop1:
         softmax_top1(logits ? logits : (const float*)acts_[op.in], B, num_classes_, num_classes_, idx_out, prob_out, s);
         break;
+      case Kernel::SoftmaxTopK:  // on the logits the tail wrote
+        softmax_topk(logits ? logits : (const float*)acts_[logits_act_], B, num_classes_, num_classes_, st.count, idx,
+                     prob, s);
+        break;
     }
     if (st.side) {
       DMLC_HIP_CHECK(hipEventRecord(join_evs_[oi], side_));
@@ -1650,7 +1666,15 @@ void Engine::run_ops(const std::vector<Step>& steps, const uint8_t* images, int 
 
 void Engine::forward(const uint8_t* images, int B, int Hin, int Win, int32_t* idx, float* prob,
                      float* logits, hipStream_t stream, bool use_graph) {
+  forward_topk(images, B, Hin, Win, 1, idx, prob, logits, stream, use_graph);
+}
+
+void Engine::forward_topk(const uint8_t* images, int B, int Hin, int Win, int k, int32_t* idx, float* prob,
+                          float* logits, hipStream_t stream, bool use_graph) {
   if (B <= 0) return;
+  if (k < 1 || k > std::min(num_classes_, kMaxTopK))
+    throw std::invalid_argument("top-k: k must be in 1..min(num_classes, " + std::to_string(kMaxTopK) + ")");
+  if (k > 1 && (!idx || !prob)) throw std::invalid_argument("top-k: null idx / prob");
   if (B > max_batch_) throw std::invalid_argument("batch exceeds reserved max_batch");
   if (!images) throw std::invalid_argument("null images");
   DMLC_HIP_CHECK(hipSetDevice(device_));
@@ -1663,10 +1687,10 @@ void Engine::forward(const uint8_t* images, int B, int Hin, int Win, int32_t* id
     // engine's stream and back (two cross-stream waits cost ~40 us of idle
     // GPU between back-to-back forwards: profiles/r1_graph_gap.txt). The
     // engine's own stream is only used to capture.
-    GraphKey key{images, B, Hin, Win, idx, prob, logits};
+    GraphKey key{images, B, Hin, Win, idx, prob, logits, k};
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
-      const std::vector<Step> steps = plan(B, native, opt_.fork_ds, false);
+      const std::vector<Step> steps = plan(B, native, opt_.fork_ds, false, k);
       DMLC_HIP_CHECK(hipStreamSynchronize(stream));
       hipGraph_t g;
       DMLC_HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
@@ -1681,7 +1705,7 @@ void Engine::forward(const uint8_t* images, int B, int Hin, int Win, int32_t* id
     DMLC_HIP_CHECK(hipGraphLaunch(it->second, stream));
   } else {  // eager launches straight onto the caller's stream
     DMLC_TRACE("engine.forward");
-    run_ops(plan(B, native, opt_.fork_ds, true), images, B, Hin, Win, idx, prob, logits, stream, nullptr, true);
+    run_ops(plan(B, native, opt_.fork_ds, true, k), images, B, Hin, Win, idx, prob, logits, stream, nullptr, true);
   }
   DMLC_HIP_CHECK(hipEventRecord(ev_out_, stream));
   last_stream_ = stream;

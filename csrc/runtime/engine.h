@@ -177,7 +177,7 @@ enum class Kernel {
   None,  // nothing to launch: the op is computed inside another step, or not needed
   AlexStem, StemPoolU8, StemPool, FcSmall, Conv1x1Cat, Conv1x1Chain, Bottleneck56, Bottleneck56Head, Block,
   S2Rows, S2Rows128, Stream, Stream8, Rows28, Rows, Small, Direct13, Direct27, Conv1x1, BigTile, Igemm, FcGemm,
-  HeadPooled, HeadFused, AvgPoolGlobal, AvgPoolAdaptive, MaxPool, Preprocess, SoftmaxTop1
+  HeadPooled, HeadFused, AvgPoolGlobal, AvgPoolAdaptive, MaxPool, Preprocess, SoftmaxTop1, SoftmaxTopK
 };
 const char* kernel_name(Kernel k);
 
@@ -193,7 +193,7 @@ struct Step {
   bool store_y = true;   // false: the last op's activation is not written (Stream with the pool fused, under a graph)
   bool side = false;     // runs on the side stream (fork_ds)
   int cfg = -1;          // BigTile: tile config
-  int count = 0;         // Rows / StemPool / StemPoolU8: strip; Small: mf; BigTile / FcGemm: K splits
+  int count = 0;         // Rows / StemPool / StemPoolU8: strip; Small: mf; BigTile / FcGemm: K splits; SoftmaxTopK: k
 };
 
 class Engine {
@@ -226,10 +226,12 @@ class Engine {
   // spin on each other and need their CUs); keep_acts: every activation a
   // test may read is stored (eager / profile runs; a graph capture drops the
   // last conv's when its pool is fused). Host integer logic only.
-  std::vector<Step> plan(int B, bool native, bool side, bool keep_acts) const;
-  // The plan a graph-captured forward(B, Hin, Win) runs.
-  std::vector<Step> plan(int B, int Hin, int Win) const {
-    return plan(B, Hin == image_size_ && Win == image_size_, opt_.fork_ds, false);
+  // topk > 1 (forward_topk): the same steps, then one SoftmaxTopK step on the
+  // logits the tail wrote; it belongs to the last op and covers none (n_ops 0).
+  std::vector<Step> plan(int B, bool native, bool side, bool keep_acts, int topk = 1) const;
+  // The plan a graph-captured forward(B, Hin, Win) / forward_topk(.., topk) runs.
+  std::vector<Step> plan(int B, int Hin, int Win, int topk = 1) const {
+    return plan(B, Hin == image_size_ && Win == image_size_, opt_.fork_ds, false, topk);
   }
   // A step's extra fields as text, e.g. "ds=layer2.0.downsample.0 wreg".
   std::string step_detail(const Step& st) const;
@@ -244,7 +246,7 @@ class Engine {
   static std::vector<PlanLine> plan_audit(const std::string& arch, const WeightMap& weights,
                                           const EngineOptions& options, int B, bool native, int num_cus,
                                           std::vector<Op>* engine_ops = nullptr, int num_classes = 1000,
-                                          int image_size = 224);
+                                          int image_size = 224, int topk = 1);
   std::vector<PlanLine> plan_lines(const std::vector<Step>& steps) const;
   void* weight_arena() const { return warena_; }
 
@@ -270,6 +272,12 @@ class Engine {
   // (B, pointers) signature (captured on first use).
   void forward(const uint8_t* images, int B, int Hin, int Win, int32_t* idx, float* prob,
                float* logits, hipStream_t stream, bool use_graph);
+  // The same forward with the k best classes per image: idx int32 [B, k] and
+  // prob f32 [B, k] in descending order (softmax_topk's contract), 1 <= k <=
+  // min(num_classes, kMaxTopK). k = 1 is forward(); for k > 1 the tail's own
+  // top-1 goes to engine scratch and one more kernel ranks the logits.
+  void forward_topk(const uint8_t* images, int B, int Hin, int Win, int k, int32_t* idx, float* prob,
+                    float* logits, hipStream_t stream, bool use_graph);
 
   // Eager forward with an event pair around every op: (op name, ms).
   std::vector<std::pair<std::string, float>> profile(const uint8_t* images, int B, int Hin,
@@ -300,7 +308,8 @@ class Engine {
   void mark_fp8();
   void calibrate(const WeightMap& w);
   // Launch the steps of plan(B, native, ...) in order. evs: an event after
-  // every op (profile); trace: a host trace range per launching op.
+  // every op (profile); trace: a host trace range per launching op. In a plan
+  // that ends with SoftmaxTopK, idx / prob are that step's [B, k] outputs.
   void run_ops(const std::vector<Step>& steps, const uint8_t* images, int B, int Hin, int Win, int32_t* idx,
                float* prob, float* logits, hipStream_t s, std::vector<hipEvent_t>* evs, bool trace);
   // A conv op's launch arguments in two parts: the geometry (shapes, padding,
@@ -336,7 +345,7 @@ class Engine {
   void* bt_ws_ = nullptr;  // big-tile conv split-K hand-off flags + partial-tile slabs
   size_t bt_ws_bytes_ = 0;
   void* zero_ = nullptr;  // 16-B zero page: LDS-DMA source for conv padding taps
-  int32_t* dummy_idx_ = nullptr;
+  int32_t* dummy_idx_ = nullptr;  // idx [max_batch] + prob [max_batch] nobody reads (profile; the tail's top-1 under top-k)
   void* head_ws_ = nullptr;  // fused head partials + per-group tickets
   size_t head_ws_bytes_ = 0;
 
@@ -347,7 +356,7 @@ class Engine {
   bool last_stream_valid_ = false;
   hipStream_t side_ = nullptr;                      // downsample branch
   std::vector<hipEvent_t> fork_evs_, join_evs_;     // per op
-  using GraphKey = std::tuple<const void*, int, int, int, void*, void*, void*>;
+  using GraphKey = std::tuple<const void*, int, int, int, void*, void*, void*, int>;  // ..., logits, k
   std::map<GraphKey, hipGraphExec_t> graphs_;
 };
 

@@ -636,6 +636,27 @@ def softmax_top1(logits: torch.Tensor, n: int | None = None) -> tuple[torch.Tens
     return idx, prob
 
 
+def softmax_topk(logits: torch.Tensor, k: int, n: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The k largest of the first n columns of fp32 logits [B, ld], per row:
+    (idx int32 [B, k], prob f32 [B, k]) in descending order, equal logits by
+    ascending class; prob is the softmax over those n columns. Column 0 is
+    bit-equal to ``softmax_top1``. 1 <= k <= min(n, MAX_TOPK)."""
+    _need_cuda(logits)
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise ValueError("softmax_topk expects 2-D fp32 logits")
+    B, ld = logits.shape
+    n = ld if n is None else n
+    C = native()
+    if not 1 <= n <= ld:
+        raise ValueError(f"softmax_topk: n = {n} outside 1..{ld}")
+    if not isinstance(k, int) or not 1 <= k <= min(n, C.MAX_TOPK):
+        raise ValueError(f"softmax_topk: k = {k} outside 1..min(n = {n}, {C.MAX_TOPK})")
+    idx = torch.empty(B, k, device=logits.device, dtype=torch.int32)
+    prob = torch.empty(B, k, device=logits.device, dtype=torch.float32)
+    C.softmax_topk(_ptr(logits.contiguous()), B, n, ld, k, _ptr(idx), _ptr(prob), _stream())
+    return idx, prob
+
+
 # ---------------------------------------------------------------- split JPEG decode
 def _align(n: int, a: int = 256) -> int:
     return (n + a - 1) // a * a

@@ -44,6 +44,7 @@ class InferenceEngine:
         self.max_batch = max_batch
         self.num_classes = num_classes
         self.image_size = image_size
+        self.max_topk = min(num_classes, C.MAX_TOPK)  # largest predict(topk=)
 
     @property
     def gflop_per_image(self) -> float:
@@ -53,24 +54,41 @@ class InferenceEngine:
     def weight_bytes(self) -> int:
         return self._e.weight_bytes
 
-    def predict(self, images: torch.Tensor, use_graph: bool = True, out=None, return_logits: bool = False):
+    def predict(self, images: torch.Tensor, use_graph: bool = True, out=None, return_logits: bool = False,
+                topk: int = 1):
         """images: uint8 [B,H,W,3] on this engine's GPU. Returns (idx int32 [B],
-        prob f32 [B]) (+ logits f32 [B,num_classes] if return_logits)."""
+        prob f32 [B]) (+ logits f32 [B,num_classes] if return_logits). topk > 1:
+        idx and prob are [B,topk], the best classes in descending order (equal
+        logits by ascending class), and ``out`` must be contiguous tensors of
+        that shape; 1 <= topk <= min(num_classes, MAX_TOPK)."""
         if images.device != self.device or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
             raise ValueError(f"expected uint8 [B,H,W,3] on {self.device}, got {images.dtype} {tuple(images.shape)} "
                              f"on {images.device}")
         if not images.is_contiguous():
             raise ValueError("images must be contiguous")
         B, H, W, _ = images.shape
+        if not isinstance(topk, int) or not 1 <= topk <= self.max_topk:
+            raise ValueError(f"topk = {topk} outside 1..{self.max_topk}")
         if out is None:
-            idx = torch.empty(B, dtype=torch.int32, device=self.device)
-            prob = torch.empty(B, dtype=torch.float32, device=self.device)
+            shape = (B,) if topk == 1 else (B, topk)
+            idx = torch.empty(shape, dtype=torch.int32, device=self.device)
+            prob = torch.empty(shape, dtype=torch.float32, device=self.device)
         else:
             idx, prob = out
+            if topk > 1:
+                for t, dt in ((idx, torch.int32), (prob, torch.float32)):
+                    if (t.device != self.device or t.dtype != dt or tuple(t.shape) != (B, topk)
+                            or not t.is_contiguous()):
+                        raise ValueError(f"out: expected contiguous {dt} [{B},{topk}] on {self.device}, got "
+                                         f"{t.dtype} {tuple(t.shape)} on {t.device}")
         logits = torch.empty(B, self.num_classes, dtype=torch.float32, device=self.device) if return_logits else None
-        self._e.forward(images.data_ptr(), B, H, W, idx.data_ptr(), prob.data_ptr(),
-                        0 if logits is None else logits.data_ptr(),
-                        torch.cuda.current_stream(self.device).cuda_stream, use_graph)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        lp = 0 if logits is None else logits.data_ptr()
+        if topk == 1:
+            self._e.forward(images.data_ptr(), B, H, W, idx.data_ptr(), prob.data_ptr(), lp, stream, use_graph)
+        else:
+            self._e.forward_topk(images.data_ptr(), B, H, W, topk, idx.data_ptr(), prob.data_ptr(), lp, stream,
+                                 use_graph)
         return (idx, prob, logits) if return_logits else (idx, prob)
 
     def profile(self, images: torch.Tensor) -> list[tuple[str, float]]:
