@@ -415,6 +415,28 @@ PYBIND11_MODULE(_C, m) {
     std::copy(img.rgb.begin(), img.rgb.end(), a.mutable_data());
     return a;
   });
+  // ragged resize: descs = packed ImageDesc records (device memory), out u8 [B, S, S, 3]
+  m.attr("IMAGE_DESC_BYTES") = (int)sizeof(ImageDesc);
+  m.def("resize_u8_ragged", [](uintptr_t descs, uintptr_t out, int B, int S_, uintptr_t stream, bool antialias) {
+    resize_u8_ragged(P<ImageDesc>(descs), P<uint8_t>(out), B, S_, S(stream), antialias);
+  }, py::arg("descs"), py::arg("out"), py::arg("B"), py::arg("S"), py::arg("stream"), py::arg("antialias") = false);
+  // its host reference: u8 [H, W, 3] -> u8 [S, S, 3]
+  m.def("resize_u8_host", [](const py::array_t<uint8_t, py::array::c_style | py::array::forcecast>& rgb, int S_,
+                             bool antialias) {
+    if (rgb.ndim() != 3 || rgb.shape(2) != 3) throw std::invalid_argument("resize_u8_host: expected u8 [H, W, 3]");
+    Image img;
+    img.height = (int)rgb.shape(0);
+    img.width = (int)rgb.shape(1);
+    img.rgb.assign(rgb.data(), rgb.data() + rgb.size());
+    std::vector<uint8_t> r;
+    {
+      py::gil_scoped_release nogil;
+      r = resize_u8_host(img, S_, antialias);
+    }
+    py::array_t<uint8_t> a({S_, S_, 3});
+    std::copy(r.begin(), r.end(), a.mutable_data());
+    return a;
+  }, py::arg("rgb"), py::arg("size"), py::arg("antialias") = false);
   // split decode: entropy decoding on the host -> (layout, int16 coefficients)
   m.def("decode_jpeg_coeffs", [](py::bytes data) {
     std::string s = data;

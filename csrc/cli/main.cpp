@@ -364,6 +364,7 @@ void handle_line(Node& n, const std::string& line) {
                  std::to_string(cs.entries) + " bytes " + std::to_string(cs.bytes) + " capacity " +
                  std::to_string(cs.capacity) + " prefetched " + std::to_string(n.member->prefetched()));
         out_line("jpeg gpu " + std::to_string(cs.jpeg_gpu) + " cpu " + std::to_string(cs.jpeg_cpu));
+        if (ex->resize_antialias()) out_line("resize antialias on");
       }
     } else if (c == "prefetch") {
       // stage the dataset's query images into the executor's (HBM) cache
@@ -421,7 +422,7 @@ int run_node(const Args& a) {
     }
     ex = make_executor(a.get("executor", "auto"), devs, a.geti("max-batch", 256),
                        (size_t)a.geti("hbm-cache-mb", 4096) << 20, a.geti("min-shard", 32), a.geti("lanes", 2),
-                       a.geti("batch-window-us", 200), a.has("jpeg-gpu"));
+                       a.geti("batch-window-us", 200), a.has("jpeg-gpu"), a.has("resize-antialias"));
     if (ex) {
       // the GPUs are split between the jobs in this order (first floor(n/2)
       // to the first job, src/services.rs:199-211)
@@ -504,14 +505,17 @@ int run_classify(const Args& a) {
   const std::vector<std::string> paths = split(a.get("image"), ',');
   // --jpeg-gpu: the executor reads the files itself and finishes their decode on the GPU
   const bool jpeg_gpu = a.has("jpeg-gpu");
+  // --resize-antialias: images that are not 224 x 224 are shrunk with the antialiased filter
+  const bool resize_aa = a.has("resize-antialias");
   std::vector<Image> imgs;
   if (!jpeg_gpu)
     for (const auto& p : paths) imgs.push_back(decode_jpeg_file(p));
   // all images in one batch (one forward on the GPU executor)
   const int max_batch = std::max<int>(1, (int)paths.size());
   auto ex = jpeg_gpu ? make_executor(a.get("executor", "cpu"), std::vector<int>{a.geti("device", 0)}, max_batch,
-                                     (size_t)4 << 30, 32, 2, 200, true)
-                     : make_executor(a.get("executor", "cpu"), a.geti("device", 0), max_batch);
+                                     (size_t)4 << 30, 32, 2, 200, true, resize_aa)
+                     : make_executor(a.get("executor", "cpu"), a.geti("device", 0), max_batch, (size_t)4 << 30,
+                                     resize_aa);
   if (!ex) throw std::runtime_error("no inference executor in this build");
   ex->load_model(model, a.get("weights"));
   const Labels labels = Labels::load(a.get("labels", "synset_words.txt"));
@@ -543,10 +547,12 @@ int main(int argc, char** argv) {
                  "                 [--max-attempts 3] [--watch-ms 250] [--query-timeout-ms 120000]\n"
                  "                 [--query-timeout-min-ms 1000]\n"
                  "                 [--max-batch 256] [--batch-window-us 200] [--hbm-cache-mb 4096] [--prefetch]\n"
-                 "                 [--jpeg-gpu]\n"
+                 "                 [--jpeg-gpu] [--resize-antialias]\n"
                  "       dmlc-node selftest\n"
                  "       dmlc-node classify --model M --weights W.ot --labels L --image I.JPEG [--executor cpu|gpu]\n"
-                 "                      [--jpeg-gpu]\n";
+                 "                      [--jpeg-gpu] [--resize-antialias]\n"
+                 "  --resize-antialias  shrink query images that are not 224x224 with the antialiased (support-\n"
+                 "                      stretched) bilinear filter instead of the two-tap rule (node and classify)\n";
     return 0;
   }
   return run_node(parse(argc, argv, 1));

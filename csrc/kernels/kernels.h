@@ -149,12 +149,15 @@ void preprocess_u8(const uint8_t* x, void* y, int B, int Hin, int Win, int S, in
 
 // Ragged batch: image b = descs[b] (device memory, u8 HWC at its own size)
 // -> out u8 [B, S, S, 3], same resize rule as preprocess_u8, rounded to u8
-// (S % 4 == 0).
+// (S % 4 == 0). antialias: the triangle filter is stretched by max(scale, 1)
+// per axis (torch's / PIL's antialias=True bilinear; resize_u8_host is the host
+// reference), so shrinking averages the source instead of sampling four pixels
+// per output; enlarging is the same two-tap rule either way.
 struct ImageDesc {
   const uint8_t* ptr;
   int h, w;
 };
-void resize_u8_ragged(const ImageDesc* descs, uint8_t* out, int B, int S, hipStream_t s);
+void resize_u8_ragged(const ImageDesc* descs, uint8_t* out, int B, int S, hipStream_t s, bool antialias = false);
 
 // The GPU half of the split JPEG decode (jpeg_finish.hip) over a ragged batch:
 // entropy-decoded coefficients (decode_jpeg_coeffs) -> RGB u8 HWC. Image i =

@@ -852,4 +852,105 @@ Image decode_jpeg_file(const std::string& path) {
   return decode_jpeg(buf.data(), buf.size());
 }
 
+namespace {
+
+// One axis of the antialiased filter (csrc/kernels/resize.hip has the same
+// struct): centre, 1 / support and the taps [lo, hi) of output index i.
+struct AaAxis {
+  float c, inv_sup, inv_norm;
+  int lo, hi;
+  float weight(int j) const { return std::max(0.f, 1.f - std::fabs((j - c + 0.5f) * inv_sup)); }
+};
+
+AaAxis aa_axis(int i, int n_in, int n_out) {
+  const float scale = (float)n_in / (float)n_out, sup = std::max(scale, 1.f);
+  AaAxis a;
+  a.c = scale * (i + 0.5f);
+  a.inv_sup = 1.f / sup;
+  a.lo = std::max(0, (int)(a.c - sup + 0.5f));
+  a.hi = std::min(n_in, (int)(a.c + sup + 0.5f));
+  float t = 0.f;
+  for (int j = a.lo; j < a.hi; ++j) t += a.weight(j);
+  a.inv_norm = t > 0.f ? 1.f / t : 0.f;
+  return a;
+}
+
+uint8_t to_u8(float v) { return (uint8_t)std::min(std::max(std::nearbyint(v), 0.f), 255.f); }
+
+}  // namespace
+
+std::vector<uint8_t> resize_u8_host(const Image& img, int S, bool antialias) {
+  const int Hin = img.height, Win = img.width;
+  if (S <= 0 || Hin <= 0 || Win <= 0 || img.rgb.size() != (size_t)Hin * Win * 3)
+    throw std::invalid_argument("resize_u8_host: bad image or size");
+  std::vector<uint8_t> out((size_t)S * S * 3);
+  if (Hin == S && Win == S) {
+    std::memcpy(out.data(), img.rgb.data(), out.size());
+    return out;
+  }
+  int RH, RW;
+  if (Hin <= Win) {
+    RH = S;
+    RW = (int)((long)S * Win / Hin);
+  } else {
+    RW = S;
+    RH = (int)((long)S * Hin / Win);
+  }
+  const int oy = (RH - S) / 2, ox = (RW - S) / 2;
+  const uint8_t* rgb = img.rgb.data();
+  if (!antialias) {
+    // the two-tap rule of preprocess_host / resize_ragged_kernel, same arithmetic
+    const float sys = (float)Hin / RH, sxs = (float)Win / RW;
+    for (int y = 0; y < S; ++y)
+      for (int x = 0; x < S; ++x) {
+        float sy = (y + oy + 0.5f) * sys - 0.5f, sx = (x + ox + 0.5f) * sxs - 0.5f;
+        sy = std::min(std::max(sy, 0.f), (float)(Hin - 1));
+        sx = std::min(std::max(sx, 0.f), (float)(Win - 1));
+        const int y0 = (int)sy, x0 = (int)sx, y1 = std::min(y0 + 1, Hin - 1), x1 = std::min(x0 + 1, Win - 1);
+        const float fy = sy - y0, fx = sx - x0;
+        for (int k = 0; k < 3; ++k) {
+          const float a = rgb[((size_t)y0 * Win + x0) * 3 + k], b = rgb[((size_t)y0 * Win + x1) * 3 + k];
+          const float d = rgb[((size_t)y1 * Win + x0) * 3 + k], e = rgb[((size_t)y1 * Win + x1) * 3 + k];
+          const float top = a + (b - a) * fx, bot = d + (e - d) * fx;
+          out[((size_t)y * S + x) * 3 + k] = to_u8(top + (bot - top) * fy);
+        }
+      }
+    return out;
+  }
+  // separable, like the kernel: every source row the crop touches is filtered
+  // horizontally once and added into the output rows it contributes to; fp32,
+  // one rounding at the end
+  std::vector<AaAxis> ax(S), ay(S);
+  for (int i = 0; i < S; ++i) {
+    ax[i] = aa_axis(i + ox, Win, RW);
+    ay[i] = aa_axis(i + oy, Hin, RH);
+  }
+  std::vector<float> acc((size_t)S * S * 3, 0.f), hrow((size_t)S * 3);
+  int yb = 0;  // first output row whose taps may still include r
+  for (int r = ay[0].lo; r < ay[S - 1].hi; ++r) {
+    const uint8_t* row = rgb + (size_t)r * Win * 3;
+    for (int x = 0; x < S; ++x) {
+      const AaAxis& a = ax[x];
+      float h0 = 0.f, h1 = 0.f, h2 = 0.f;
+      for (int j = a.lo; j < a.hi; ++j) {
+        const float w = a.weight(j);
+        h0 += w * row[j * 3];
+        h1 += w * row[j * 3 + 1];
+        h2 += w * row[j * 3 + 2];
+      }
+      hrow[x * 3] = h0 * a.inv_norm;
+      hrow[x * 3 + 1] = h1 * a.inv_norm;
+      hrow[x * 3 + 2] = h2 * a.inv_norm;
+    }
+    while (yb < S && ay[yb].hi <= r) ++yb;
+    for (int y = yb; y < S && ay[y].lo <= r; ++y) {  // (lo and hi do not decrease with y)
+      const float wy = ay[y].weight(r) * ay[y].inv_norm;
+      float* o = &acc[(size_t)y * S * 3];
+      for (int i = 0; i < S * 3; ++i) o[i] += wy * hrow[i];
+    }
+  }
+  for (size_t i = 0; i < out.size(); ++i) out[i] = to_u8(acc[i]);
+  return out;
+}
+
 }  // namespace dmlc

@@ -28,6 +28,15 @@ Image decode_jpeg_file(const std::string& path);
 // copy; saves the Image vector's zero-fill and a copy per query image).
 void decode_jpeg_into(const uint8_t* data, size_t size, const std::function<uint8_t*(int, int)>& out);
 
+// The serving resize on the host: short side -> S (long = floor(S*long/short)),
+// centre crop, bilinear with half-pixel centres, rounded to u8 [S, S, 3] HWC;
+// an S x S image is copied. antialias = false is the two-tap rule of
+// preprocess_host and resize_ragged_kernel. antialias = true stretches the
+// triangle filter by max(scale, 1) per axis (torch's / PIL's antialias=True
+// bilinear; same rule and fp32 arithmetic as resize_ragged_aa_kernel in
+// csrc/kernels/resize.hip), with no rounding between the two axes.
+std::vector<uint8_t> resize_u8_host(const Image& img, int S, bool antialias);
+
 // ---- split decode: entropy decoding here, IDCT and colour on the GPU
 // (csrc/kernels/jpeg_finish.hip).
 struct JpegComp {

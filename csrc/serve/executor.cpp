@@ -30,8 +30,16 @@
 
 namespace dmlc {
 
-std::vector<float> preprocess_host(const Image& img, int S) {
+std::vector<float> preprocess_host(const Image& img, int S, bool antialias) {
   const int Hin = img.height, Win = img.width;
+  if (antialias) {
+    const std::vector<uint8_t> u8 = resize_u8_host(img, S, true);
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    std::vector<float> out((size_t)3 * S * S);
+    for (size_t p = 0; p < (size_t)S * S; ++p)
+      for (int k = 0; k < 3; ++k) out[(size_t)k * S * S + p] = ((float)u8[p * 3 + k] / 255.f - mean[k]) / stdv[k];
+    return out;
+  }
   int RH, RW;
   if (Hin <= Win) {
     RH = S;
@@ -41,6 +49,8 @@ std::vector<float> preprocess_host(const Image& img, int S) {
     RH = (int)((long)S * Hin / Win);
   }
   const int oy = (RH - S) / 2, ox = (RW - S) / 2;
+  // (the two-tap arithmetic below has a twin that stops at the u8:
+  // resize_u8_host(img, S, false) in csrc/runtime/jpeg.cpp; keep them in step)
   const float sys = (float)Hin / RH, sxs = (float)Win / RW;
   const bool identity = Hin == S && Win == S;
   const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
@@ -82,7 +92,9 @@ namespace {
 // ------------------------------------------------------------------ CPU
 class CpuExecutor : public Executor {
  public:
+  explicit CpuExecutor(bool resize_antialias = false) : resize_aa_(resize_antialias) {}
   std::string backend() const override { return "cpu"; }
+  bool resize_antialias() const override { return resize_aa_; }
 
   void load_model(const std::string& model, const std::string& path) override {
     load_model_weights(model, ot_load(path));
@@ -109,7 +121,7 @@ class CpuExecutor : public Executor {
     const int S = 224;
     at::Tensor x = at::empty({(int64_t)imgs.size(), 3, S, S}, at::kFloat);
     for (size_t i = 0; i < imgs.size(); ++i) {
-      auto v = preprocess_host(imgs[i], S);
+      auto v = preprocess_host(imgs[i], S, resize_aa_);
       std::memcpy(x[i].data_ptr<float>(), v.data(), v.size() * 4);
     }
     at::Tensor logits = forward(model, it->second, x);
@@ -185,6 +197,7 @@ class CpuExecutor : public Executor {
     return at::linear(x, W(w, "fc.weight"), W(w, "fc.bias"));
   }
 
+  const bool resize_aa_;
   mutable std::mutex mu_;
   std::map<std::string, TM> models_;
 };
@@ -210,9 +223,9 @@ class CpuExecutor : public Executor {
 class GpuExecutor : public Executor {
  public:
   GpuExecutor(std::vector<int> devices, int max_batch, size_t cache_bytes, int min_shard, int lanes, int batch_window_us,
-              bool jpeg_gpu)
+              bool jpeg_gpu, bool resize_antialias)
       : devices_(std::move(devices)), max_batch_(max_batch), lanes_(std::max(1, std::min(lanes, 4))),
-        jpeg_gpu_(jpeg_gpu), cache_cap_(cache_bytes) {
+        jpeg_gpu_(jpeg_gpu), resize_aa_(resize_antialias), cache_cap_(cache_bytes) {
     if (devices_.empty()) throw std::invalid_argument("GpuExecutor: no devices");
     kernel_stagger_for_lanes(lanes_);  // (one lane: the stream convs staggered, stagger.hip)
     for (int d : devices_) cache_bytes_dev_[d] = 0;
@@ -254,6 +267,7 @@ class GpuExecutor : public Executor {
     }
     return s.empty() ? "none" : s;
   }
+  bool resize_antialias() const override { return resize_aa_; }
   void set_jobs(const std::vector<std::string>& models) override { fleet_->set_jobs(models); }
   void lose_device(int device) override {
     fleet_->lose(device);
@@ -649,7 +663,7 @@ class GpuExecutor : public Executor {
       if (hd[i].h <= 0 || hd[i].w <= 0 || hd[i].h > 4096 || hd[i].w > 4096)
         throw std::runtime_error("resize_into: bad image size");
     DMLC_HIP_CHECK(hipMemcpyAsync(c.aux, hd, (size_t)cnt * sizeof(ImageDesc), hipMemcpyHostToDevice, s));
-    resize_u8_ragged((const ImageDesc*)c.aux, (uint8_t*)c.batch, (int)cnt, kS, s);
+    resize_u8_ragged((const ImageDesc*)c.aux, (uint8_t*)c.batch, (int)cnt, kS, s, resize_aa_);
   }
 
   std::shared_ptr<HbmBlob> blob(const std::string& key) const {
@@ -1026,7 +1040,7 @@ class GpuExecutor : public Executor {
 
   std::vector<int> devices_;
   int max_batch_, lanes_;
-  const bool jpeg_gpu_;
+  const bool jpeg_gpu_, resize_aa_;
   std::set<std::pair<int, int>> peers_;  // (reader, owner) with peer access enabled
   std::unique_ptr<dp::Fleet> fleet_;
   std::mutex weights_mu_;
@@ -1048,20 +1062,22 @@ class GpuExecutor : public Executor {
 
 std::unique_ptr<Executor> make_executor(const std::string& backend, const std::vector<int>& devices, int max_batch,
                                         size_t cache_bytes, int min_shard, int lanes, int batch_window_us,
-                                        bool jpeg_gpu) {
+                                        bool jpeg_gpu, bool resize_antialias) {
   std::string b = backend;
   if (b == "auto") b = hip_device_count() > 0 ? "gpu" : "cpu";
   if (b == "gpu") {
     for (int d : devices)
       if (d < 0 || hip_device_count() <= d) throw std::runtime_error("no HIP device " + std::to_string(d));
-    return std::make_unique<GpuExecutor>(devices, max_batch, cache_bytes, min_shard, lanes, batch_window_us, jpeg_gpu);
+    return std::make_unique<GpuExecutor>(devices, max_batch, cache_bytes, min_shard, lanes, batch_window_us, jpeg_gpu,
+                                         resize_antialias);
   }
-  if (b == "cpu") return std::make_unique<CpuExecutor>();
+  if (b == "cpu") return std::make_unique<CpuExecutor>(resize_antialias);
   throw std::invalid_argument("unknown executor backend: " + backend);
 }
 
-std::unique_ptr<Executor> make_executor(const std::string& backend, int device, int max_batch, size_t cache_bytes) {
-  return make_executor(backend, std::vector<int>{device}, max_batch, cache_bytes, 32, 2);
+std::unique_ptr<Executor> make_executor(const std::string& backend, int device, int max_batch, size_t cache_bytes,
+                                        bool resize_antialias) {
+  return make_executor(backend, std::vector<int>{device}, max_batch, cache_bytes, 32, 2, 200, false, resize_antialias);
 }
 
 }  // namespace dmlc

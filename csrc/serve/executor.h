@@ -82,6 +82,8 @@ class Executor {
   // lost (the fleet rebalances over the survivors).
   virtual void set_jobs(const std::vector<std::string>& models) { (void)models; }
   virtual std::string placement() const { return backend(); }
+  // make_executor's resize_antialias
+  virtual bool resize_antialias() const { return false; }
   virtual void lose_device(int device) {
     (void)device;
     throw std::runtime_error("lose_device: not a multi-GPU executor");
@@ -94,8 +96,11 @@ class Executor {
 
 // backend: "gpu", "cpu" or "auto" (GPU when a HIP device is visible).
 // cache_bytes: HBM budget for decoded images (GPU executor).
+// resize_antialias (off by default): images that are not already 224 x 224 are
+// resized with the antialiased filter (resize_u8_ragged / resize_u8_host with
+// antialias = true) instead of the two-tap bilinear rule.
 std::unique_ptr<Executor> make_executor(const std::string& backend, int device, int max_batch,
-                                        size_t cache_bytes = (size_t)4 << 30);
+                                        size_t cache_bytes = (size_t)4 << 30, bool resize_antialias = false);
 // Several GPUs of this node (GPU executor, csrc/comm/fleet.h): the GPUs are
 // split between the loaded models; a query goes to the least-loaded GPU of
 // its model's partition, and a batch of >= 2 x min_shard images is scattered
@@ -111,12 +116,13 @@ std::unique_ptr<Executor> make_executor(const std::string& backend, int device, 
 // kernels do not handle keep the host decoder.
 std::unique_ptr<Executor> make_executor(const std::string& backend, const std::vector<int>& devices, int max_batch,
                                         size_t cache_bytes, int min_shard, int lanes = 2, int batch_window_us = 200,
-                                        bool jpeg_gpu = false);
+                                        bool jpeg_gpu = false, bool resize_antialias = false);
 int hip_device_count();
 
 // Host-side reference preprocessing (same rule as csrc/kernels/preprocess.hip):
 // short side -> S (long = floor(S*long/short)), centre crop, bilinear
 // align_corners=False, /255, ImageNet mean/std. Output CHW float [3,S,S].
-std::vector<float> preprocess_host(const Image& img, int S);
+// antialias: the resize is resize_u8_host(img, S, true) instead.
+std::vector<float> preprocess_host(const Image& img, int S, bool antialias = false);
 
 }  // namespace dmlc

@@ -91,14 +91,14 @@ class DigestExecutor final : public Executor {
 
 }  // namespace
 
-std::unique_ptr<Executor> make_executor(const std::string& backend, int, int, size_t) {
+std::unique_ptr<Executor> make_executor(const std::string& backend, int, int, size_t, bool) {
   if (backend == "none") return nullptr;
   if (backend == "digest" || backend == "auto" || backend == "cpu") return std::make_unique<DigestExecutor>();
   throw std::runtime_error("executor '" + backend + "' is not available in the sanitizer build");
 }
 
 std::unique_ptr<Executor> make_executor(const std::string& backend, const std::vector<int>& devices, int max_batch,
-                                        size_t cache_bytes, int, int, int, bool) {
+                                        size_t cache_bytes, int, int, int, bool, bool) {
   return make_executor(backend, devices.empty() ? 0 : devices[0], max_batch, cache_bytes);
 }
 

@@ -678,6 +678,42 @@ def _upload(parts, device) -> tuple[torch.Tensor, list[int]]:
     return stage.to(device, non_blocking=True), offs
 
 
+def resize_u8_ragged(images, size: int = 224, antialias: bool = False) -> torch.Tensor:
+    """Differently sized u8 [H, W, 3] images on one GPU -> one u8 batch
+    [B, size, size, 3] in one launch (csrc/kernels/resize.hip): short side ->
+    size, long side floor(size * long / short), centre crop, bilinear with
+    half-pixel centres, rounded to u8; a size x size image is copied. With
+    ``antialias`` the triangle filter is stretched by max(scale, 1) per axis
+    (torch's ``antialias=True``), so shrinking averages the source instead of
+    sampling four pixels per output; ``native().resize_u8_host`` is the host
+    reference of both."""
+    import numpy as np
+    images = list(images)
+    if not images:
+        raise ValueError("resize_u8_ragged: no images")
+    if not isinstance(size, int) or size <= 0 or size % 4 != 0:
+        raise ValueError(f"resize_u8_ragged: size = {size} is not a positive multiple of 4")
+    _need_cuda(*images)
+    dev = images[0].device
+    for t in images:
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"resize_u8_ragged expects uint8 [H, W, 3] images, got {t.dtype} {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError("resize_u8_ragged expects contiguous images")
+        if t.device != dev:
+            raise ValueError("resize_u8_ragged expects every image on the same device")
+    C = native()
+    descs = np.zeros(len(images), dtype=np.dtype([("ptr", "<u8"), ("h", "<i4"), ("w", "<i4")]))
+    assert descs.dtype.itemsize == C.IMAGE_DESC_BYTES
+    for i, t in enumerate(images):
+        descs[i] = (t.data_ptr(), t.shape[0], t.shape[1])
+    with torch.cuda.device(dev):
+        d, _ = _upload([descs], dev)
+        out = torch.empty(len(images), size, size, 3, device=dev, dtype=torch.uint8)
+        C.resize_u8_ragged(_ptr(d), _ptr(out), len(images), size, _stream(), bool(antialias))
+    return out
+
+
 def jpeg_idct(coeffs, qt, bw: int, bh: int, device="cuda") -> torch.Tensor:
     """Stage 1 of the GPU JPEG finish on one plane: quantised int16
     coefficients [bh][bw][64] (natural order) and a quantisation table (64

@@ -48,9 +48,12 @@ def shard_info(path: str) -> dict:
     return {"n": n, "h": h, "w": w, "label0": label0 if flags & 1 else None}
 
 
-def decode_resize(files: list[str], size: int = 224) -> np.ndarray:
+def decode_resize(files: list[str], size: int = 224, antialias: bool = False) -> np.ndarray:
     """Decode JPEGs (the native decoder) and resize them the way the engine
-    does (short side -> size, centre crop, bilinear, u8): [n, size, size, 3]."""
+    does (short side -> size, centre crop, bilinear, u8): [n, size, size, 3].
+    ``antialias``: the way a node started with --resize-antialias does (the
+    native ``resize_u8_host(..., antialias=True)``: the filter widens when it
+    shrinks)."""
     import torch
     import torch.nn.functional as F
     from .. import native
@@ -58,6 +61,9 @@ def decode_resize(files: list[str], size: int = 224) -> np.ndarray:
     out = np.empty((len(files), size, size, 3), dtype=np.uint8)
     for i, p in enumerate(files):
         img = C.decode_jpeg(open(p, "rb").read())
+        if antialias:
+            out[i] = C.resize_u8_host(img, size, True)
+            continue
         h, w, _ = img.shape
         if h <= w:
             rh, rw = size, size * w // h

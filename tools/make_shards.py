@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--synthetic", type=int, default=0,
                     help="N random 224x224 images (labels 0..N-1) instead of a dataset (throughput runs on a box "
                          "without the reference's JPEGs)")
+    ap.add_argument("--antialias", action="store_true",
+                    help="shrink with the antialiased filter, as a node started with --resize-antialias does")
     a = ap.parse_args()
     from dmlc.utils.shards import decode_resize, write_shard
     if a.synthetic:
@@ -54,7 +56,7 @@ def main():
         files.append(os.path.join(d, sorted(os.listdir(d))[0]))  # the first file, as src/services.rs:485-490
     os.makedirs(a.out, exist_ok=True)
     for k, s in enumerate(range(0, len(files), a.per)):
-        imgs = decode_resize(files[s:s + a.per])
+        imgs = decode_resize(files[s:s + a.per], antialias=a.antialias)
         p = write_shard(os.path.join(a.out, f"{a.name}.{k}.u8s"), imgs, label0=s)
         print(f"{p}: images {s}..{s + len(imgs) - 1} ({os.path.getsize(p) / 1e6:.1f} MB)", flush=True)
 
