@@ -265,6 +265,16 @@ PYBIND11_MODULE(_C, m) {
          bool paired) { preprocess_u8(P<uint8_t>(x), P<void>(y), B, Hin, Win, S_, pad, Wr, S(stream), paired); },
       py::arg("x"), py::arg("y"), py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("S"), py::arg("pad"),
       py::arg("Wr"), py::arg("stream"), py::arg("paired") = false);
+  py::enum_<TensorDType>(m, "TensorDType")
+      .value("F32", TensorDType::F32)
+      .value("F16", TensorDType::F16)
+      .value("BF16", TensorDType::BF16);
+  m.def(
+      "pack_tensor",
+      [](uintptr_t x, TensorDType dt, bool channels_last, uintptr_t y, int B, int S_, int pad, int Wr, bool paired,
+         uintptr_t stream) { pack_tensor(P<void>(x), dt, channels_last, P<void>(y), B, S_, pad, Wr, paired, S(stream)); },
+      py::arg("x"), py::arg("dtype"), py::arg("channels_last"), py::arg("y"), py::arg("B"), py::arg("S"),
+      py::arg("pad"), py::arg("Wr"), py::arg("paired"), py::arg("stream"));
   m.attr("STEM_POOL_K") = kStemPoolK;
   m.def("stem_pool_pick_strip", &stem_pool_pick_strip);
   m.def("stem_pool_u8_pick_strip", &stem_pool_u8_pick_strip);
@@ -557,14 +567,15 @@ PYBIND11_MODULE(_C, m) {
     return l;
   };
   m.def("plan_audit", [=](const std::string& arch, const py::dict& weights, const std::map<std::string, bool>& options,
-                          int B, bool native, int num_cus, int num_classes, int image_size, int topk) {
+                          int B, bool native, int num_cus, int num_classes, int image_size, int topk,
+                          bool tensor_in) {
     std::vector<Op> ops;
     const auto lines = Engine::plan_audit(arch, to_weight_map(weights), engine_options(options), B, native, num_cus,
-                                          &ops, num_classes, image_size, topk);
+                                          &ops, num_classes, image_size, topk, tensor_in);
     return py::make_tuple(plan_list(lines), op_list(ops));
   }, py::arg("arch"), py::arg("weights"), py::arg("options") = std::map<std::string, bool>{}, py::arg("B") = 256,
      py::arg("native") = true, py::arg("num_cus") = 256, py::arg("num_classes") = 1000, py::arg("image_size") = 224,
-     py::arg("topk") = 1);
+     py::arg("topk") = 1, py::arg("tensor_in") = false);
   py::class_<Engine>(m, "Engine")
       .def(py::init([](const std::string& arch, const py::dict& weights, int device, int num_classes,
                        int image_size, const std::map<std::string, bool>& options) {
@@ -601,6 +612,16 @@ PYBIND11_MODULE(_C, m) {
           py::arg("images"), py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("k"), py::arg("idx"),
           py::arg("prob"), py::arg("logits"), py::arg("stream"), py::arg("use_graph") = true,
           py::call_guard<py::gil_scoped_release>())
+      .def(
+          "forward_tensor",
+          [](Engine& e, uintptr_t x, TensorDType dt, bool channels_last, int B, int k, uintptr_t idx, uintptr_t prob,
+             uintptr_t logits, uintptr_t stream, bool use_graph) {
+            e.forward_tensor(P<void>(x), dt, channels_last, B, k, P<int32_t>(idx), P<float>(prob), P<float>(logits),
+                             S(stream), use_graph);
+          },
+          py::arg("x"), py::arg("dtype"), py::arg("channels_last"), py::arg("B"), py::arg("k"), py::arg("idx"),
+          py::arg("prob"), py::arg("logits"), py::arg("stream"), py::arg("use_graph") = true,
+          py::call_guard<py::gil_scoped_release>())
       .def("profile",
            [](Engine& e, uintptr_t images, int B, int Hin, int Win, uintptr_t stream) {
              return e.profile(P<uint8_t>(images), B, Hin, Win, S(stream));
@@ -612,9 +633,9 @@ PYBIND11_MODULE(_C, m) {
              return py::make_tuple(s.H, s.W, s.C, s.f32);
            })
       .def("op_list", [=](const Engine& e) { return op_list(e.ops()); })
-      .def("plan", [=](const Engine& e, int B, int Hin, int Win, int topk) {
-        return plan_list(e.plan_lines(e.plan(B, Hin, Win, topk)));
-      }, py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("topk") = 1)
+      .def("plan", [=](const Engine& e, int B, int Hin, int Win, int topk, bool tensor_in) {
+        return plan_list(e.plan_lines(e.plan(B, Hin, Win, topk, tensor_in)));
+      }, py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("topk") = 1, py::arg("tensor_in") = false)
       .def_property_readonly("num_cus", &Engine::num_cus)
       .def_property_readonly("num_activations", &Engine::num_activations)
       .def_property_readonly("arch", &Engine::arch)

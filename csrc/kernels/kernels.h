@@ -147,6 +147,17 @@ void avgpool_adaptive(const void* x, void* y, int B, int H, int W, int C, int Ho
 void preprocess_u8(const uint8_t* x, void* y, int B, int Hin, int Win, int S, int pad, int Wr,
                    hipStream_t s, bool paired = false);
 
+// Float tensor -> the same packed image (pack_tensor.hip), byte for byte
+// preprocess_u8's layout for (S, pad, Wr, paired): x is [B, 3, S, S]
+// contiguous, or [B, S, S, 3] contiguous with channels_last, of dtype dt. The
+// values go in as given (no resize, normalisation or clamping), rounded to
+// bf16 to nearest even (fp16 through fp32; bf16 copied); all padding of y is
+// written as zero on every launch. x needs its element's alignment only.
+enum class TensorDType { F32, F16, BF16 };
+size_t tensor_dtype_bytes(TensorDType dt);
+void pack_tensor(const void* x, TensorDType dt, bool channels_last, void* y, int B, int S, int pad, int Wr,
+                 bool paired, hipStream_t s);
+
 // Ragged batch: image b = descs[b] (device memory, u8 HWC at its own size)
 // -> out u8 [B, S, S, 3], same resize rule as preprocess_u8, rounded to u8
 // (S % 4 == 0). antialias: the triangle filter is stretched by max(scale, 1)

@@ -163,12 +163,12 @@ std::vector<PackRegion> Engine::pack_audit(const std::string& arch, const Weight
 std::vector<Engine::PlanLine> Engine::plan_audit(const std::string& arch, const WeightMap& weights,
                                                  const EngineOptions& options, int B, bool native, int num_cus,
                                                  std::vector<Op>* engine_ops, int num_classes, int image_size,
-                                                 int topk) {
+                                                 int topk, bool tensor_in) {
   Engine e(HostOnly{}, arch, weights, num_classes, image_size, options);
   e.num_cus_ = num_cus;
   e.layout_weights();
   if (engine_ops) *engine_ops = e.ops_;
-  return e.plan_lines(e.plan(B, native, options.fork_ds, false, topk));
+  return e.plan_lines(e.plan(B, native, options.fork_ds, false, topk, tensor_in));
 }
 
 // Same graph, packing and calibration as `src`, on another device, with an
@@ -930,7 +930,7 @@ const char* kernel_name(Kernel k) {
       "None", "AlexStem", "StemPoolU8", "StemPool", "FcSmall", "Conv1x1Cat", "Conv1x1Chain", "Bottleneck56",
       "Bottleneck56Head", "Block", "S2Rows", "S2Rows128", "Stream", "Stream8", "Rows28", "Rows", "Small", "Direct13",
       "Direct27", "Conv1x1", "BigTile", "Igemm", "FcGemm", "HeadPooled", "HeadFused", "AvgPoolGlobal",
-      "AvgPoolAdaptive", "MaxPool", "Preprocess", "SoftmaxTop1", "SoftmaxTopK"};
+      "AvgPoolAdaptive", "MaxPool", "Preprocess", "PackTensor", "SoftmaxTop1", "SoftmaxTopK"};
   static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::SoftmaxTopK + 1, "one name per Kernel");
   return names[(size_t)k];
 }
@@ -1347,7 +1347,9 @@ struct Engine::Planner {
     }
   }
 
-  std::vector<Step> run(bool native, bool side, bool keep_acts, int topk) {
+  std::vector<Step> run(bool native, bool side, bool keep_acts, int topk, bool tensor_in) {
+    // a float tensor takes the resized-input plan: the u8 stems cannot read it
+    if (tensor_in) native = false;
     // never a side stream next to a big-tile conv
     const bool side_ready = side && std::find(path.begin(), path.end(), Path::BigTile) == path.end();
     for (size_t oi = 0; oi < ops.size(); oi = steps.back().first_op + steps.back().n_ops) {
@@ -1362,7 +1364,7 @@ struct Engine::Planner {
           else if (native && opt.fused_preprocess && op.k == 1)
             emit(Kernel::None, oi, 1);
           else
-            emit(Kernel::Preprocess, oi, 1);
+            emit(tensor_in ? Kernel::PackTensor : Kernel::Preprocess, oi, 1);
           break;
         case OpType::Conv:
           plan_conv(oi, side_ready, keep_acts);
@@ -1416,10 +1418,10 @@ struct Engine::Planner {
   }
 };
 
-std::vector<Step> Engine::plan(int B, bool native, bool side, bool keep_acts, int topk) const {
+std::vector<Step> Engine::plan(int B, bool native, bool side, bool keep_acts, int topk, bool tensor_in) const {
   if (topk < 1 || topk > std::min(num_classes_, kMaxTopK))
     throw std::invalid_argument("top-k: k must be in 1..min(num_classes, " + std::to_string(kMaxTopK) + ")");
-  return Planner(*this, B).run(native, side, keep_acts, topk);
+  return Planner(*this, B).run(native, side, keep_acts, topk, tensor_in);
 }
 
 std::string Engine::step_detail(const Step& st) const {
@@ -1446,8 +1448,17 @@ std::vector<Engine::PlanLine> Engine::plan_lines(const std::vector<Step>& steps)
 }
 
 // ---------------------------------------------------------------- executor
-void Engine::run_ops(const std::vector<Step>& steps, const uint8_t* images, int B, int Hin, int Win, int32_t* idx,
-                     float* prob, float* logits, hipStream_t s, std::vector<hipEvent_t>* evs, bool trace) {
+void Engine::run_ops(const std::vector<Step>& steps, const Input& in, int B, int32_t* idx, float* prob,
+                     float* logits, hipStream_t s, std::vector<hipEvent_t>* evs, bool trace) {
+  // the u8 kernels and PackTensor each read their own kind of input: a plan
+  // made for the other kind is refused before anything is launched
+  for (const Step& st : steps) {
+    const bool u8 = st.kernel == Kernel::AlexStem || st.kernel == Kernel::Preprocess || st.kernel == Kernel::StemPoolU8;
+    if ((u8 && in.tensor) || (st.kernel == Kernel::PackTensor && !in.tensor))
+      throw std::logic_error(std::string("plan step ") + kernel_name(st.kernel) + " does not read this input");
+  }
+  const uint8_t* const images = in.tensor ? nullptr : (const uint8_t*)in.data;
+  const int Hin = in.Hin, Win = in.Win;
   size_t ei = 0;
   if (evs) DMLC_HIP_CHECK(hipEventRecord((*evs)[ei++], s));
   std::map<int, hipEvent_t> joined;  // activation -> event its side-stream producer recorded
@@ -1495,6 +1506,12 @@ void Engine::run_ops(const std::vector<Step>& steps, const uint8_t* images, int 
         const bool paired = op.k == 1;
         const int Wr = paired ? 2 * shapes_[op.out].W : shapes_[op.out].W;
         preprocess_u8(images, acts_[op.out], B, Hin, Win, image_size_, op.pad, Wr, s, paired);
+        break;
+      }
+      case Kernel::PackTensor: {
+        const bool paired = op.k == 1;
+        const int Wr = paired ? 2 * shapes_[op.out].W : shapes_[op.out].W;
+        pack_tensor(in.data, in.dt, in.channels_last, acts_[op.out], B, image_size_, op.pad, Wr, paired, s);
         break;
       }
       case Kernel::StemPoolU8:
@@ -1671,13 +1688,36 @@ void Engine::forward(const uint8_t* images, int B, int Hin, int Win, int32_t* id
 
 void Engine::forward_topk(const uint8_t* images, int B, int Hin, int Win, int k, int32_t* idx, float* prob,
                           float* logits, hipStream_t stream, bool use_graph) {
+  Input in;
+  in.data = images;
+  in.Hin = Hin;
+  in.Win = Win;
+  forward_input(in, B, k, idx, prob, logits, stream, use_graph);
+}
+
+void Engine::forward_tensor(const void* x, TensorDType dt, bool channels_last, int B, int k, int32_t* idx,
+                            float* prob, float* logits, hipStream_t stream, bool use_graph) {
+  if (dt != TensorDType::F32 && dt != TensorDType::F16 && dt != TensorDType::BF16)
+    throw std::invalid_argument("forward_tensor: unknown dtype");
+  Input in;
+  in.data = x;
+  in.Hin = in.Win = image_size_;
+  in.tensor = true;
+  in.dt = dt;
+  in.channels_last = channels_last;
+  forward_input(in, B, k, idx, prob, logits, stream, use_graph);
+}
+
+void Engine::forward_input(const Input& in, int B, int k, int32_t* idx, float* prob, float* logits,
+                           hipStream_t stream, bool use_graph) {
   if (B <= 0) return;
   if (k < 1 || k > std::min(num_classes_, kMaxTopK))
     throw std::invalid_argument("top-k: k must be in 1..min(num_classes, " + std::to_string(kMaxTopK) + ")");
   if (k > 1 && (!idx || !prob)) throw std::invalid_argument("top-k: null idx / prob");
   if (B > max_batch_) throw std::invalid_argument("batch exceeds reserved max_batch");
-  if (!images) throw std::invalid_argument("null images");
+  if (!in.data) throw std::invalid_argument("null images");
   DMLC_HIP_CHECK(hipSetDevice(device_));
+  const int Hin = in.Hin, Win = in.Win;
   const bool native = Hin == image_size_ && Win == image_size_;
   // Forwards share the activation arena: one on a different stream than the
   // previous forward is ordered after it (an event, only then).
@@ -1687,14 +1727,14 @@ void Engine::forward_topk(const uint8_t* images, int B, int Hin, int Win, int k,
     // engine's stream and back (two cross-stream waits cost ~40 us of idle
     // GPU between back-to-back forwards: profiles/r1_graph_gap.txt). The
     // engine's own stream is only used to capture.
-    GraphKey key{images, B, Hin, Win, idx, prob, logits, k};
+    GraphKey key{in.data, B, Hin, Win, idx, prob, logits, k, in.kind()};
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
-      const std::vector<Step> steps = plan(B, native, opt_.fork_ds, false, k);
+      const std::vector<Step> steps = plan(B, native, opt_.fork_ds, false, k, in.tensor);
       DMLC_HIP_CHECK(hipStreamSynchronize(stream));
       hipGraph_t g;
       DMLC_HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-      run_ops(steps, images, B, Hin, Win, idx, prob, logits, stream_, nullptr, false);
+      run_ops(steps, in, B, idx, prob, logits, stream_, nullptr, false);
       DMLC_HIP_CHECK(hipStreamEndCapture(stream_, &g));
       hipGraphExec_t ex;
       DMLC_HIP_CHECK(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
@@ -1705,7 +1745,7 @@ void Engine::forward_topk(const uint8_t* images, int B, int Hin, int Win, int k,
     DMLC_HIP_CHECK(hipGraphLaunch(it->second, stream));
   } else {  // eager launches straight onto the caller's stream
     DMLC_TRACE("engine.forward");
-    run_ops(plan(B, native, opt_.fork_ds, true, k), images, B, Hin, Win, idx, prob, logits, stream, nullptr, true);
+    run_ops(plan(B, native, opt_.fork_ds, true, k, in.tensor), in, B, idx, prob, logits, stream, nullptr, true);
   }
   DMLC_HIP_CHECK(hipEventRecord(ev_out_, stream));
   last_stream_ = stream;
@@ -1720,8 +1760,12 @@ std::vector<std::pair<std::string, float>> Engine::profile(const uint8_t* images
   std::vector<hipEvent_t> evs(ops_.size() + 1);
   for (auto& e : evs) DMLC_HIP_CHECK(hipEventCreate(&e));
   // per-op event timing keeps every op on one stream
-  run_ops(plan(B, Hin == image_size_ && Win == image_size_, false, true), images, B, Hin, Win, nullptr, nullptr, nullptr,
-          stream_, &evs, true);
+  Input in;
+  in.data = images;
+  in.Hin = Hin;
+  in.Win = Win;
+  run_ops(plan(B, Hin == image_size_ && Win == image_size_, false, true), in, B, nullptr, nullptr, nullptr, stream_, &evs,
+          true);
   DMLC_HIP_CHECK(hipStreamSynchronize(stream_));
   std::vector<std::pair<std::string, float>> out;
   for (size_t i = 0; i < ops_.size(); ++i) {

@@ -177,7 +177,7 @@ enum class Kernel {
   None,  // nothing to launch: the op is computed inside another step, or not needed
   AlexStem, StemPoolU8, StemPool, FcSmall, Conv1x1Cat, Conv1x1Chain, Bottleneck56, Bottleneck56Head, Block,
   S2Rows, S2Rows128, Stream, Stream8, Rows28, Rows, Small, Direct13, Direct27, Conv1x1, BigTile, Igemm, FcGemm,
-  HeadPooled, HeadFused, AvgPoolGlobal, AvgPoolAdaptive, MaxPool, Preprocess, SoftmaxTop1, SoftmaxTopK
+  HeadPooled, HeadFused, AvgPoolGlobal, AvgPoolAdaptive, MaxPool, Preprocess, PackTensor, SoftmaxTop1, SoftmaxTopK
 };
 const char* kernel_name(Kernel k);
 
@@ -228,10 +228,14 @@ class Engine {
   // last conv's when its pool is fused). Host integer logic only.
   // topk > 1 (forward_topk): the same steps, then one SoftmaxTopK step on the
   // logits the tail wrote; it belongs to the last op and covers none (n_ops 0).
-  std::vector<Step> plan(int B, bool native, bool side, bool keep_acts, int topk = 1) const;
-  // The plan a graph-captured forward(B, Hin, Win) / forward_topk(.., topk) runs.
-  std::vector<Step> plan(int B, int Hin, int Win, int topk = 1) const {
-    return plan(B, Hin == image_size_ && Win == image_size_, opt_.fork_ds, false, topk);
+  // tensor_in (forward_tensor): the native = false plan step for step, with
+  // PackTensor in place of Preprocess (the u8 stems never run; `native` is
+  // not looked at).
+  std::vector<Step> plan(int B, bool native, bool side, bool keep_acts, int topk = 1, bool tensor_in = false) const;
+  // The plan a graph-captured forward(B, Hin, Win) / forward_topk(.., topk) /
+  // forward_tensor (tensor_in) runs.
+  std::vector<Step> plan(int B, int Hin, int Win, int topk = 1, bool tensor_in = false) const {
+    return plan(B, Hin == image_size_ && Win == image_size_, opt_.fork_ds, false, topk, tensor_in);
   }
   // A step's extra fields as text, e.g. "ds=layer2.0.downsample.0 wreg".
   std::string step_detail(const Step& st) const;
@@ -246,7 +250,7 @@ class Engine {
   static std::vector<PlanLine> plan_audit(const std::string& arch, const WeightMap& weights,
                                           const EngineOptions& options, int B, bool native, int num_cus,
                                           std::vector<Op>* engine_ops = nullptr, int num_classes = 1000,
-                                          int image_size = 224, int topk = 1);
+                                          int image_size = 224, int topk = 1, bool tensor_in = false);
   std::vector<PlanLine> plan_lines(const std::vector<Step>& steps) const;
   void* weight_arena() const { return warena_; }
 
@@ -278,6 +282,14 @@ class Engine {
   // top-1 goes to engine scratch and one more kernel ranks the logits.
   void forward_topk(const uint8_t* images, int B, int Hin, int Win, int k, int32_t* idx, float* prob,
                     float* logits, hipStream_t stream, bool use_graph);
+  // The same forward on a float tensor the caller has already normalised:
+  // x is device [B, 3, S, S] contiguous, or [B, S, S, 3] contiguous with
+  // channels_last, S = image_size(), of dtype dt (pack_tensor's contract: the
+  // values are used as given). k = 1: forward()'s outputs; k > 1:
+  // forward_topk()'s. Graphs are keyed by the input kind as well, so a u8 and
+  // a tensor forward, or two dtypes, on one pointer never replay each other's.
+  void forward_tensor(const void* x, TensorDType dt, bool channels_last, int B, int k, int32_t* idx, float* prob,
+                      float* logits, hipStream_t stream, bool use_graph);
 
   // Eager forward with an event pair around every op: (op name, ms).
   std::vector<std::pair<std::string, float>> profile(const uint8_t* images, int B, int Hin,
@@ -310,8 +322,20 @@ class Engine {
   // Launch the steps of plan(B, native, ...) in order. evs: an event after
   // every op (profile); trace: a host trace range per launching op. In a plan
   // that ends with SoftmaxTopK, idx / prob are that step's [B, k] outputs.
-  void run_ops(const std::vector<Step>& steps, const uint8_t* images, int B, int Hin, int Win, int32_t* idx,
-               float* prob, float* logits, hipStream_t s, std::vector<hipEvent_t>* evs, bool trace);
+  // What a forward reads: u8 [B, Hin, Win, 3] images, or a float tensor
+  // [B, 3, S, S] / channels_last [B, S, S, 3] (Hin = Win = image_size_).
+  struct Input {
+    const void* data = nullptr;
+    int Hin = 0, Win = 0;
+    bool tensor = false;
+    TensorDType dt = TensorDType::F32;
+    bool channels_last = false;
+    int kind() const { return tensor ? 1 + 2 * (int)dt + (channels_last ? 1 : 0) : 0; }  // graph key
+  };
+  void run_ops(const std::vector<Step>& steps, const Input& in, int B, int32_t* idx, float* prob, float* logits,
+               hipStream_t s, std::vector<hipEvent_t>* evs, bool trace);
+  void forward_input(const Input& in, int B, int k, int32_t* idx, float* prob, float* logits, hipStream_t stream,
+                     bool use_graph);
   // A conv op's launch arguments in two parts: the geometry (shapes, padding,
   // flags, scales, tile, split-K, persistent grid), which is all the planner
   // and the kernels' *_supported checks see, and the operands (x, w, bias,
@@ -356,7 +380,7 @@ class Engine {
   bool last_stream_valid_ = false;
   hipStream_t side_ = nullptr;                      // downsample branch
   std::vector<hipEvent_t> fork_evs_, join_evs_;     // per op
-  using GraphKey = std::tuple<const void*, int, int, int, void*, void*, void*, int>;  // ..., logits, k
+  using GraphKey = std::tuple<const void*, int, int, int, void*, void*, void*, int, int>;  // ..., logits, k, Input::kind
   std::map<GraphKey, hipGraphExec_t> graphs_;
 };
 

@@ -515,6 +515,47 @@ def preprocess_u8(images: torch.Tensor, size: int = 224, pad: int = 0, row_width
     return y
 
 
+_TENSOR_DTYPES = {torch.float32: "F32", torch.float16: "F16", torch.bfloat16: "BF16"}
+
+
+def tensor_input(x: torch.Tensor, size: int | None = None):
+    """Check a float image tensor [B,3,S,S] (S = ``size`` if given) in
+    float32 / float16 / bfloat16, laid out contiguous or ``torch.channels_last``,
+    and return (native dtype, channels_last). Anything else is a ValueError."""
+    want = f"float32/float16/bfloat16 [B,3,{size or 'S'},{size or 'S'}], contiguous or channels_last"
+    if x.dtype not in _TENSOR_DTYPES or x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] \
+            or (size is not None and x.shape[2] != size):
+        raise ValueError(f"expected {want}, got {x.dtype} {tuple(x.shape)}")
+    # the layout is what the strides say: both checks compare strides with the shape
+    if x.is_contiguous():
+        channels_last = False
+    elif x.is_contiguous(memory_format=torch.channels_last):
+        channels_last = True
+    else:
+        raise ValueError(f"expected {want}, got strides {tuple(x.stride())} for shape {tuple(x.shape)}")
+    return getattr(native().TensorDType, _TENSOR_DTYPES[x.dtype]), channels_last
+
+
+def pack_tensor(x: torch.Tensor, pad: int, row_width: int | None = None, paired: bool = False) -> torch.Tensor:
+    """float32 / float16 / bfloat16 [B,3,S,S] (contiguous or channels_last)
+    -> the bf16 packed RGB image ``preprocess_u8`` writes for the same
+    (S, pad, row_width, paired), from the values as given: no resize, no
+    normalisation, rounded to bf16 to nearest even, zero border."""
+    if not x.is_cuda:
+        raise ValueError("pack_tensor needs a CUDA/HIP tensor (no CPU fallback)")
+    dt, channels_last = tensor_input(x)
+    B, _, S, _ = x.shape
+    P = S + 2 * pad
+    Wr = row_width or (P + 7) // 8 * 8
+    if pad < 0 or Wr % 8 or Wr < P:
+        raise ValueError(f"pack_tensor: row_width {Wr} must be a multiple of 8 and >= S + 2 pad = {P} (pad >= 0)")
+    shape = (B, P, Wr // 2, 8) if paired else (B, P, Wr, 3)
+    y = torch.empty(*shape, device=x.device, dtype=torch.bfloat16)
+    if B:
+        native().pack_tensor(_ptr(x), dt, channels_last, _ptr(y), B, S, pad, Wr, paired, _stream())
+    return y
+
+
 def paired_image(x_nhwc3: torch.Tensor, pad: int = 3, pairs: int | None = None) -> torch.Tensor:
     """Reference construction of the fused stem's input: the zero-padded
     image [B, H+2p, 2*pairs, 3] regrouped as [B, H+2p, pairs, 8] with

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import torch
 
-from . import native
+from . import native, ops
 from .models import build, state_dict_f32
 
 
@@ -60,13 +60,31 @@ class InferenceEngine:
         prob f32 [B]) (+ logits f32 [B,num_classes] if return_logits). topk > 1:
         idx and prob are [B,topk], the best classes in descending order (equal
         logits by ascending class), and ``out`` must be contiguous tensors of
-        that shape; 1 <= topk <= min(num_classes, MAX_TOPK)."""
+        that shape; 1 <= topk <= min(num_classes, MAX_TOPK).
+
+        images may instead be a float32 / float16 / bfloat16 tensor
+        [B,3,image_size,image_size], contiguous or ``torch.channels_last``: the
+        tensor a torch model takes. It is used as given (rounded to bf16): the
+        caller resizes and normalises, with whatever mean/std the weights were
+        trained with. topk, out, return_logits and use_graph work the same."""
+        if images.is_floating_point():
+            return self._predict_tensor(images, use_graph, out, return_logits, topk)
         if images.device != self.device or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
             raise ValueError(f"expected uint8 [B,H,W,3] on {self.device}, got {images.dtype} {tuple(images.shape)} "
                              f"on {images.device}")
         if not images.is_contiguous():
             raise ValueError("images must be contiguous")
         B, H, W, _ = images.shape
+        return self._forward(("u8", images.data_ptr(), H, W), B, use_graph, out, return_logits, topk)
+
+    def _predict_tensor(self, x: torch.Tensor, use_graph, out, return_logits, topk):
+        if x.device != self.device:
+            raise ValueError(f"expected a float tensor on {self.device}, got one on {x.device}")
+        dt, channels_last = ops.tensor_input(x, self.image_size)
+        return self._forward(("tensor", x.data_ptr(), dt, channels_last), x.shape[0], use_graph, out, return_logits,
+                             topk)
+
+    def _forward(self, src, B, use_graph, out, return_logits, topk):
         if not isinstance(topk, int) or not 1 <= topk <= self.max_topk:
             raise ValueError(f"topk = {topk} outside 1..{self.max_topk}")
         if out is None:
@@ -84,11 +102,16 @@ class InferenceEngine:
         logits = torch.empty(B, self.num_classes, dtype=torch.float32, device=self.device) if return_logits else None
         stream = torch.cuda.current_stream(self.device).cuda_stream
         lp = 0 if logits is None else logits.data_ptr()
-        if topk == 1:
-            self._e.forward(images.data_ptr(), B, H, W, idx.data_ptr(), prob.data_ptr(), lp, stream, use_graph)
+        if src[0] == "tensor":
+            _, ptr, dt, channels_last = src
+            self._e.forward_tensor(ptr, dt, channels_last, B, topk, idx.data_ptr(), prob.data_ptr(), lp, stream,
+                                   use_graph)
+        elif topk == 1:
+            _, ptr, H, W = src
+            self._e.forward(ptr, B, H, W, idx.data_ptr(), prob.data_ptr(), lp, stream, use_graph)
         else:
-            self._e.forward_topk(images.data_ptr(), B, H, W, topk, idx.data_ptr(), prob.data_ptr(), lp, stream,
-                                 use_graph)
+            _, ptr, H, W = src
+            self._e.forward_topk(ptr, B, H, W, topk, idx.data_ptr(), prob.data_ptr(), lp, stream, use_graph)
         return (idx, prob, logits) if return_logits else (idx, prob)
 
     def profile(self, images: torch.Tensor) -> list[tuple[str, float]]:
