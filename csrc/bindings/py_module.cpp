@@ -283,14 +283,16 @@ PYBIND11_MODULE(_C, m) {
   m.def("conv3x3_stream", [](uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t res, uintptr_t y, uintptr_t zero,
                              int B, int H, int W, int Cin, int Cout, int stride, bool relu, uintptr_t stream,
                              uintptr_t stamps, uintptr_t wd, uintptr_t bd, uintptr_t yd, uintptr_t wfrag,
-                             uintptr_t wdfrag) {
+                             uintptr_t wdfrag, uintptr_t pool, bool store_y, float out_inv_scale) {
     conv3x3_stream(P<void>(x), P<void>(w), P<float>(bias), P<void>(res), P<void>(y), P<void>(zero), B, H, W, Cin, Cout,
                    stride, relu, S(stream), P<unsigned long long>(stamps), P<void>(wd), P<float>(bd), P<void>(yd),
-                   P<void>(wfrag), P<void>(wdfrag));
+                   P<void>(wfrag), P<void>(wdfrag), P<void>(pool), store_y, out_inv_scale);
   }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("res"), py::arg("y"), py::arg("zero"), py::arg("B"),
         py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("stride"), py::arg("relu"),
         py::arg("stream"), py::arg("stamps") = 0, py::arg("wd") = 0, py::arg("bd") = 0, py::arg("yd") = 0,
-        py::arg("wfrag") = 0, py::arg("wdfrag") = 0);
+        py::arg("wfrag") = 0, py::arg("wdfrag") = 0, py::arg("pool") = 0, py::arg("store_y") = true,
+        py::arg("out_inv_scale") = 0.f);
+  m.def("conv3x3_stream_pool_supported", &conv3x3_stream_pool_supported);
   m.def("conv3x3_stream_uses_frag", &conv3x3_stream_uses_frag);
   m.def("conv3x3_stream_set_variant", &conv3x3_stream_set_variant);
   m.def("conv3x3_rows_supported", &conv3x3_rows_supported);
@@ -316,6 +318,35 @@ PYBIND11_MODULE(_C, m) {
                  P<float>(b3), P<void>(y), res_scale, out_inv_scale, B, S(stream));
   }, py::arg("x"), py::arg("w1"), py::arg("a1"), py::arg("b1"), py::arg("wf2"), py::arg("b2"), py::arg("wf3"),
      py::arg("b3"), py::arg("y"), py::arg("res_scale"), py::arg("out_inv_scale"), py::arg("B"), py::arg("stream") = 0);
+  // AlexNet's shape-specialised kernels
+  m.attr("ALEX_STEM_K") = kAlexStemK;
+  m.def("alex_stem_k", &alex_stem_k);
+  m.def("alex_stem_supported", &alex_stem_supported);
+  m.def("alex_stem_u8", [](uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, int B, uintptr_t stream) {
+    alex_stem_u8(P<uint8_t>(x), P<void>(w), P<float>(bias), P<void>(y), B, S(stream));
+  }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("B"), py::arg("stream"));
+  m.def("conv5x5_27_supported", &conv5x5_27_supported);
+  m.def("conv5x5_27", [](uintptr_t x, uintptr_t wf, uintptr_t bias, uintptr_t y, uintptr_t zero, int B,
+                         uintptr_t stream, uintptr_t ypool) {
+    conv5x5_27(P<void>(x), P<void>(wf), P<float>(bias), P<void>(y), P<void>(zero), B, S(stream), P<void>(ypool));
+  }, py::arg("x"), py::arg("wf"), py::arg("bias"), py::arg("y"), py::arg("zero"), py::arg("B"), py::arg("stream"),
+        py::arg("ypool") = 0);
+  m.def("conv3x3_13_supported", &conv3x3_13_supported);
+  m.def("conv3x3_13_pool_supported", &conv3x3_13_pool_supported);
+  m.def("conv3x3_13", [](uintptr_t x, uintptr_t wf, uintptr_t bias, uintptr_t y, uintptr_t zero, int B, int Cin,
+                         int Cout, bool relu, uintptr_t stream, uintptr_t ypool) {
+    conv3x3_13(P<void>(x), P<void>(wf), P<float>(bias), P<void>(y), P<void>(zero), B, Cin, Cout, relu, S(stream),
+               P<void>(ypool));
+  }, py::arg("x"), py::arg("wf"), py::arg("bias"), py::arg("y"), py::arg("zero"), py::arg("B"), py::arg("Cin"),
+        py::arg("Cout"), py::arg("relu"), py::arg("stream"), py::arg("ypool") = 0);
+  m.def("fc_small_supported", &fc_small_supported);
+  m.def("fc_small", [](uintptr_t x, int ldx, uintptr_t w, int ldw, uintptr_t bias, uintptr_t y, int ldo, bool out_f32,
+                       int B, int K, int N, int Npad, bool relu, uintptr_t stream) {
+    fc_small(P<void>(x), ldx, P<void>(w), ldw, P<float>(bias), P<void>(y), ldo, out_f32, B, K, N, Npad, relu,
+             S(stream));
+  }, py::arg("x"), py::arg("ldx"), py::arg("w"), py::arg("ldw"), py::arg("bias"), py::arg("y"), py::arg("ldo"),
+        py::arg("out_f32"), py::arg("B"), py::arg("K"), py::arg("N"), py::arg("Npad"), py::arg("relu"),
+        py::arg("stream"));
   m.def("conv3x3_stream8_supported", &conv3x3_stream8_supported);
   m.def("conv3x3_stream8_frag_offset", &conv3x3_stream8_frag_offset);
   m.def("conv3x3_stream8_set_variant", &conv3x3_stream8_set_variant);
@@ -378,6 +409,16 @@ PYBIND11_MODULE(_C, m) {
   });
   m.def("head_ws_bytes", &head_ws_bytes);
   m.def("head_pooled_splits", &head_pooled_splits);
+  m.def("head_splits", &head_splits);
+  m.def("head_supported", &head_supported);
+  m.def("head_fused", [](uintptr_t x, uintptr_t w, uintptr_t bias, int B, int HW, int C, int N, int ldw, int Npad,
+                         uintptr_t logits, uintptr_t idx, uintptr_t prob, uintptr_t ws, size_t ws_bytes, int num_cus,
+                         uintptr_t stream, bool in_fp8, float scale) {
+    head_fused(P<void>(x), P<void>(w), P<float>(bias), B, HW, C, N, ldw, Npad, P<float>(logits), P<int32_t>(idx),
+               P<float>(prob), P<void>(ws), ws_bytes, num_cus, S(stream), in_fp8, scale);
+  }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("B"), py::arg("HW"), py::arg("C"), py::arg("N"),
+        py::arg("ldw"), py::arg("Npad"), py::arg("logits"), py::arg("idx"), py::arg("prob"), py::arg("ws"),
+        py::arg("ws_bytes"), py::arg("num_cus"), py::arg("stream"), py::arg("in_fp8") = false, py::arg("scale") = 1.f);
   m.def("conv1x1_plan", [](bool in8, bool out8, int rb, int nw, bool res, int s, int wv, bool ch) {
     const C1Plan p = conv1x1_plan(in8, out8, rb, nw, res, s, wv, ch);
     py::dict d;

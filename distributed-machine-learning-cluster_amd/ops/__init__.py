@@ -332,7 +332,8 @@ def stream_weight_frag(w_packed: torch.Tensor, cout: int | None = None) -> torch
 
 def conv3x3_stream(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, res: torch.Tensor | None = None,
                    relu: bool = True, stride: int = 1, downsample: tuple | None = None,
-                   frag: bool | torch.Tensor = False):
+                   frag: bool | torch.Tensor = False, pool: bool = False, store_y: bool = True,
+                   out: torch.Tensor | None = None):
     """Direct 3x3/p1 conv (conv3x3_stream.hip) on NHWC bf16 with the conv2d
     packed weights; + bias (+ residual), ReLU. Stride 1: [B,28,28,128],
     [B,14,14,256], [B,7,7,512]; stride 2: [B,56,56,64] -> 128 channels,
@@ -341,14 +342,30 @@ def conv3x3_stream(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, 
     downsample=(wd_packed [Cout, Cin], bd[, wd_frag]): stride 2 only; also
     computes the 1x1/s2 conv + bias from the same resident input and returns
     (y, yd); wd_frag = stream_weight_frag(wd_packed), precomputed for graph
-    capture."""
-    _need_cuda(x, w_packed, bias, res)
+    capture.
+
+    pool (the 7x7x512 stride-1 conv only): also returns the global average
+    pool of the bf16 output, bf16 [B, Cout]: (y, pooled). With store_y=False
+    the activation is not written (y, or ``out`` if given, is left as it was)."""
+    _need_cuda(x, w_packed, bias, res, out)
     C = native()
     B, H, W, Cin = x.shape
     Cout = w_packed.shape[0]
     if not C.conv3x3_stream_supported(H, W, Cin, Cout, stride):
         raise ValueError("conv3x3_stream: unsupported shape")
-    y = torch.empty(B, H // stride, W // stride, Cout, dtype=x.dtype, device=x.device)
+    if (pool or not store_y) and not C.conv3x3_stream_pool_supported(H, W, Cin, Cout, stride):
+        raise ValueError("conv3x3_stream: the fused average pool needs the 7x7x512 stride-1 conv")
+    if not store_y and not pool:
+        raise ValueError("conv3x3_stream: store_y=False without pool computes nothing")
+    if (pool or not store_y) and downsample is not None:
+        raise ValueError("conv3x3_stream: no fused average pool with a downsample")
+    if out is None:
+        y = torch.empty(B, H // stride, W // stride, Cout, dtype=x.dtype, device=x.device)
+    else:
+        if tuple(out.shape) != (B, H // stride, W // stride, Cout) or out.dtype != x.dtype or not out.is_contiguous():
+            raise ValueError("conv3x3_stream: out must be a contiguous [B, Ho, Wo, Cout] tensor of x's dtype")
+        y = out
+    pooled = torch.empty(B, Cout, dtype=x.dtype, device=x.device) if pool else None
     stamps = 0
     if _PHASE_STAMPS:  # per-workgroup phase stamps of the stream conv (tools/conv_bench.py --stamps)
         global BT_STAMPS
@@ -372,7 +389,10 @@ def conv3x3_stream(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, 
         wdf = downsample[2] if len(downsample) > 2 else stream_weight_frag(wd)
     C.conv3x3_stream(_ptr(x.contiguous()), _ptr(w_packed.contiguous()), _ptr(bias.float().contiguous()),
                      _ptr(None if res is None else res.contiguous()), _ptr(y), _ptr(_zero_page(x.device)), B, H, W,
-                     Cin, Cout, stride, relu, _stream(), stamps, _ptr(wd), _ptr(bd), _ptr(yd), _ptr(wf), _ptr(wdf))
+                     Cin, Cout, stride, relu, _stream(), stamps, _ptr(wd), _ptr(bd), _ptr(yd), _ptr(wf), _ptr(wdf),
+                     pool=_ptr(pooled), store_y=store_y)
+    if pool:
+        return y, pooled
     return y if downsample is None else (y, yd)
 
 
@@ -663,6 +683,177 @@ def stem_conv_pool_u8(images: torch.Tensor, w_packed: torch.Tensor, bias: torch.
     C.stem_conv_pool_u8(_ptr(images.contiguous()), _ptr(w_packed.contiguous()), _ptr(bias.float().contiguous()),
                         _ptr(y), B, S, strip, _stream(), _ptr(w_dense) if w_dense is not None else 0)
     return y
+
+
+def pack_alex_stem_weight(w: torch.Tensor, scale: torch.Tensor | None = None, device=None) -> torch.Tensor:
+    """[64, 3, 11, 11] fp32 -> bf16 [64, ALEX_STEM_K] for ``alex_stem``: weight
+    (n, c, kh, kw) at k = alex_stem_k(kh, kw, c) = (6 kh + kw // 2) * 8 +
+    3 (kw % 2) + c (the paired-chunk order of alex_stem.hip), zeros elsewhere."""
+    C = native()
+    cout, cin, kh, kw = w.shape
+    if (cout, cin, kh, kw) != (64, 3, 11, 11):
+        raise ValueError("alex_stem packs a [64, 3, 11, 11] weight")
+    w = w.float()
+    if scale is not None:
+        w = w * scale.float().view(-1, 1, 1, 1)
+    k = torch.tensor([[[C.alex_stem_k(i, j, c) for j in range(kw)] for i in range(kh)] for c in range(cin)])
+    out = torch.zeros(cout, C.ALEX_STEM_K)
+    out[:, k.reshape(-1)] = w.reshape(cout, -1)
+    out = out.to(torch.bfloat16)
+    return out.to(device) if device is not None else out
+
+
+def alex_stem(images: torch.Tensor, w: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """AlexNet features.0-2 in one kernel (alex_stem.hip): u8 [B, 224, 224, 3]
+    -> ImageNet normalisation (``preprocess_u8``'s values) -> conv 11x11/s4/p2 +
+    bias -> ReLU -> maxpool 3x3/s2 -> bf16 [B, 27, 27, 64]. w:
+    ``pack_alex_stem_weight``'s bf16 [64, ALEX_STEM_K]."""
+    _need_cuda(images, w, bias)
+    C = native()
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or images.shape[1] != images.shape[2] \
+            or not C.alex_stem_supported(images.shape[1]):
+        raise ValueError("alex_stem expects uint8 [B, 224, 224, 3]")
+    if tuple(w.shape) != (64, C.ALEX_STEM_K) or w.dtype != torch.bfloat16 or not w.is_contiguous():
+        raise ValueError("alex_stem: w must be pack_alex_stem_weight's contiguous bf16 [64, ALEX_STEM_K]")
+    if bias.numel() < 64:
+        raise ValueError("alex_stem: bias holds 64 values")
+    B = images.shape[0]
+    y = torch.empty(B, 27, 27, 64, device=images.device, dtype=torch.bfloat16)
+    C.alex_stem_u8(_ptr(images.contiguous()), _ptr(w), _ptr(bias.float().contiguous()), _ptr(y), B, _stream())
+    return y
+
+
+def conv5x5_27(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, pool: bool = False) -> torch.Tensor:
+    """AlexNet features.3 (conv5x5_27.hip): relu(conv 5x5/s1/p2 + bias) on bf16
+    [B, 27, 27, 64] -> [B, 27, 27, 192]; with ``pool`` the following 3x3/s2
+    max-pool is fused and [B, 13, 13, 192] returned instead. w_packed: conv2d
+    packed weights [>= 192, 1600]."""
+    _need_cuda(x, w_packed, bias)
+    C = native()
+    B, H, W, Cin = x.shape
+    Cout = 192
+    if x.dtype != torch.bfloat16 or not C.conv5x5_27_supported(H, W, Cin, Cout, 2) or w_packed.shape[0] < Cout \
+            or w_packed.shape[1] != 25 * Cin or w_packed.dtype != torch.bfloat16 or bias.numel() < Cout:
+        raise ValueError("conv5x5_27: unsupported shape")
+    wf = stream_weight_frag(w_packed, Cout)
+    y = torch.empty((B, 13, 13, Cout) if pool else (B, H, W, Cout), dtype=x.dtype, device=x.device)
+    C.conv5x5_27(_ptr(x.contiguous()), _ptr(wf), _ptr(bias.float().contiguous()), _ptr(y), _ptr(_zero_page(x.device)),
+                 B, _stream(), _ptr(y) if pool else 0)
+    return y
+
+
+def conv3x3_13(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, relu: bool, pool: bool = False) -> torch.Tensor:
+    """AlexNet features.6 / .8 / .10 (conv3x3_13.hip): relu?(conv 3x3/s1/p1 +
+    bias) on bf16 [B, 13, 13, Cin] for (Cin, Cout) = (192, 384), (384, 256),
+    (256, 256). With ``pool`` (256 -> 256 with ReLU only) the following 3x3/s2
+    max-pool is fused and [B, 6, 6, 256] returned instead. w_packed: conv2d
+    packed weights [Cout, 9 Cin]."""
+    _need_cuda(x, w_packed, bias)
+    C = native()
+    B, H, W, Cin = x.shape
+    Cout = w_packed.shape[0]
+    if x.dtype != torch.bfloat16 or not C.conv3x3_13_supported(H, W, Cin, Cout) or w_packed.shape[1] != 9 * Cin \
+            or w_packed.dtype != torch.bfloat16 or bias.numel() < Cout:
+        raise ValueError("conv3x3_13: unsupported shape")
+    if pool and (not relu or not C.conv3x3_13_pool_supported(Cin, Cout)):
+        raise ValueError("conv3x3_13: the fused max-pool needs ReLU and Cin = Cout = 256")
+    wf = stream_weight_frag(w_packed, Cout)
+    y = torch.empty((B, 6, 6, Cout) if pool else (B, H, W, Cout), dtype=x.dtype, device=x.device)
+    C.conv3x3_13(_ptr(x.contiguous()), _ptr(wf), _ptr(bias.float().contiguous()), _ptr(y), _ptr(_zero_page(x.device)),
+                 B, Cin, Cout, relu, _stream(), _ptr(y) if pool else 0)
+    return y
+
+
+def fc_small(x: torch.Tensor, w_packed: torch.Tensor, n: int, bias: torch.Tensor, relu: bool = False,
+             out_f32: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Fully connected layer at B <= 16 rows (fc_small.hip): act(x . w[n] +
+    bias[n]). x bf16 [B, K] with unit column stride (its row stride may exceed
+    K: a column slice of a wider activation), K % 32 == 0; w_packed bf16
+    [Npad, ldw] with ldw >= K and Npad >= n rounded up to 16. Returns [B, n]
+    bf16 (fp32 with out_f32), written into ``out[:B, :n]`` if given."""
+    _need_cuda(x, w_packed, bias, out)
+    C = native()
+    if x.dim() != 2 or w_packed.dim() != 2 or x.dtype != torch.bfloat16 or w_packed.dtype != torch.bfloat16:
+        raise ValueError("fc_small expects bf16 x [B, K] and w_packed [Npad, ldw]")
+    B, K = x.shape
+    npad, ldw = w_packed.shape
+    if B == 0 or x.stride(1) != 1 or not w_packed.is_contiguous():
+        raise ValueError("fc_small: x needs rows and unit column stride, w_packed must be contiguous")
+    ldx = x.stride(0) if B > 1 else max(x.stride(0), K)
+    if not C.fc_small_supported(B, K, ldx, ldw) or n < 1 or npad < (n + 15) // 16 * 16 or bias.numel() < n \
+            or x.data_ptr() % 16:
+        raise ValueError("fc_small: unsupported shape")
+    dt = torch.float32 if out_f32 else torch.bfloat16
+    if out is None:
+        out = torch.empty(B, n, device=x.device, dtype=dt)
+    elif out.dim() != 2 or out.dtype != dt or out.shape[0] < B or out.shape[1] < n or out.stride(1) != 1 \
+            or out.stride(0) < n:
+        raise ValueError("fc_small: out must be a [>= B, >= n] tensor of the output type with unit column stride")
+    C.fc_small(_ptr(x), ldx, _ptr(w_packed), ldw, _ptr(bias.float().contiguous()), _ptr(out), out.stride(0), out_f32,
+               B, K, n, npad, relu, _stream())
+    return out[:B, :n]
+
+
+_HEAD_WS: dict = {}
+
+
+def _head_ws(device: torch.device, batch: int) -> torch.Tensor:
+    """Per-device head workspace (partials + group counters), zeroed once at
+    allocation (the kernel re-arms its counters) and reused across calls."""
+    t = _HEAD_WS.get(device.index)
+    if t is None or t.numel() < native().head_ws_bytes(batch):
+        if t is not None:
+            torch.cuda.synchronize(device)
+        t = _HEAD_WS[device.index] = torch.zeros(native().head_ws_bytes(max(batch, 256)), dtype=torch.uint8,
+                                                 device=device)
+    return t
+
+
+def head(x: torch.Tensor, w_packed: torch.Tensor, n: int, bias: torch.Tensor, pooled: bool = False,
+         in_fp8_scale: float | None = None, splits: int = 0):
+    """The classifier head in one launch (head.hip): global average pool of
+    bf16 x [B, HW, C] (or [B, H, W, C]; e4m3 dequantised by ``in_fp8_scale``,
+    C >= 2048) + fc + bias + softmax + top-1. With ``pooled`` x is the already
+    pooled bf16 [B, C] (16 images per workgroup) and ``splits`` > 0 overrides
+    the number of class splits. w_packed: bf16 [Npad, ldw], ldw >= C. Returns
+    (logits fp32 [B, n], idx int32 [B], prob fp32 [B])."""
+    _need_cuda(x, w_packed, bias)
+    C = native()
+    fp8 = in_fp8_scale is not None
+    if pooled:
+        if fp8 or x.dim() != 2 or x.dtype != torch.bfloat16:
+            raise ValueError("head: a pooled input is bf16 [B, C]")
+        B, Ch = x.shape
+        HW = 1
+    else:
+        if x.dim() not in (3, 4) or x.dtype != (FP8 if fp8 else torch.bfloat16):
+            raise ValueError("head expects bf16 (e4m3 with in_fp8_scale) [B, HW, C]")
+        if splits:
+            raise ValueError("head: splits applies to a pooled input only")
+        B, Ch = x.shape[0], x.shape[-1]
+        HW = x.numel() // max(B * Ch, 1)
+    if w_packed.dim() != 2 or w_packed.dtype != torch.bfloat16 or not w_packed.is_contiguous():
+        raise ValueError("head: w_packed must be contiguous bf16 [Npad, ldw]")
+    npad, ldw = w_packed.shape
+    if B < 1 or HW < 1 or n < 1 or not C.head_supported(Ch, n, ldw, npad) or bias.numel() < n or splits < 0 \
+            or (fp8 and Ch < 2048):
+        raise ValueError("head: unsupported shape")
+    bias = bias.float().contiguous()
+    if bias.numel() < npad:
+        bias = torch.nn.functional.pad(bias, (0, npad - bias.numel()))
+    ws = _head_ws(x.device, B)
+    logits = torch.empty(B, n, device=x.device, dtype=torch.float32)
+    idx = torch.empty(B, device=x.device, dtype=torch.int32)
+    prob = torch.empty(B, device=x.device, dtype=torch.float32)
+    cus = torch.cuda.get_device_properties(x.device).multi_processor_count
+    if pooled:
+        C.head_pooled(_ptr(x.contiguous()), _ptr(w_packed), _ptr(bias), B, Ch, n, ldw, npad, _ptr(logits), _ptr(idx),
+                      _ptr(prob), _ptr(ws), ws.numel(), cus, _stream(), ns=splits)
+    else:
+        C.head_fused(_ptr(x.contiguous()), _ptr(w_packed), _ptr(bias), B, HW, Ch, n, ldw, npad, _ptr(logits),
+                     _ptr(idx), _ptr(prob), _ptr(ws), ws.numel(), cus, _stream(), in_fp8=fp8,
+                     scale=float(in_fp8_scale) if fp8 else 1.0)
+    return logits, idx, prob
 
 
 def softmax_top1(logits: torch.Tensor, n: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
