@@ -384,10 +384,12 @@ PYBIND11_MODULE(_C, m) {
         py::arg("stream"), py::arg("wdf") = 0, py::arg("bd") = 0, py::arg("yd") = 0);
   m.def("conv3x3_rows28_supported", &conv3x3_rows28_supported);
   m.def("conv3x3_rows28", [](uintptr_t x, uintptr_t wf, uintptr_t bias, uintptr_t res, uintptr_t y, int B, bool relu,
-                             uintptr_t stream) {
-    conv3x3_rows28(P<void>(x), P<void>(wf), P<float>(bias), P<void>(res), P<void>(y), B, relu, S(stream));
+                             uintptr_t stream, float out_inv_scale, uintptr_t xds, uintptr_t wds, uintptr_t bds) {
+    conv3x3_rows28(P<void>(x), P<void>(wf), P<float>(bias), P<void>(res), P<void>(y), B, relu, S(stream),
+                   out_inv_scale, P<void>(xds), P<void>(wds), P<float>(bds));
   }, py::arg("x"), py::arg("wf"), py::arg("bias"), py::arg("res"), py::arg("y"), py::arg("B"), py::arg("relu"),
-        py::arg("stream"));
+        py::arg("stream"), py::arg("out_inv_scale") = 0.f, py::arg("xds") = 0, py::arg("wds") = 0,
+        py::arg("bds") = 0);
   m.def("stem_conv_pool_u8", [](uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, int B, int S_, int strip,
                                 uintptr_t stream, uintptr_t w_dense) {
     stem_conv_pool_u8(P<uint8_t>(x), P<void>(w), P<float>(bias), P<void>(y), B, S_, strip, S(stream),
@@ -397,6 +399,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("stem_dense_k_index", &stem_dense_k_index);
   m.def("stem_conv_pool_set_dbg", &stem_conv_pool_set_dbg);
   m.def("stem_conv_pool_set_stamps", [](uintptr_t p) { stem_conv_pool_set_stamps((void*)p); });
+  // StaggerKernel families (kernels.h), for kernel_stagger / kernel_stagger_set
+  m.attr("STAG_STREAM") = (int)kStagStream;
+  m.attr("STAG_ROWS28") = (int)kStagRows28;
   m.def("kernel_stagger", &kernel_stagger);
   m.def("kernel_stagger_set", &kernel_stagger_set);
   m.def("kernel_stagger_for_lanes", &kernel_stagger_for_lanes);

@@ -218,26 +218,32 @@ def conv3x3_block(x: torch.Tensor, w1_packed: torch.Tensor, b1: torch.Tensor, w2
     return y
 
 
-def conv3x3_s2rows(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, wd_packed: torch.Tensor,
-                   bd: torch.Tensor, relu: bool = True):
+def conv3x3_s2rows(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, wd_packed: torch.Tensor | None,
+                   bd: torch.Tensor | None, relu: bool = True):
     """ResNet layer2.0's stride-2 3x3 conv [B,56,56,64] -> [B,28,28,128]
     and its 1x1/s2 downsample in one row-streaming kernel
     (conv3x3_s2rows.hip): returns (relu?(conv3x3(x) + bias), conv1x1_s2(x)
-    + bd). w_packed: conv2d packed weights [128, 576]; wd_packed [128, 64]."""
+    + bd). w_packed: conv2d packed weights [128, 576]; wd_packed [128, 64].
+    wd_packed = bd = None: the conv alone (the downsample then belongs to
+    ``conv3x3_rows28(downsample=)``), returns y only."""
     _need_cuda(x, w_packed, bias, wd_packed, bd)
     C = native()
     B, H, W, Cin = x.shape
     Cout = w_packed.shape[0]
+    if (wd_packed is None) != (bd is None):
+        raise ValueError("conv3x3_s2rows: wd_packed and bd go together")
     if (not C.conv3x3_s2rows_supported(H, W, Cin, Cout) or tuple(w_packed.shape) != (Cout, 9 * Cin)
-            or tuple(wd_packed.shape) != (Cout, Cin)):
+            or (wd_packed is not None and tuple(wd_packed.shape) != (Cout, Cin))):
         raise ValueError("conv3x3_s2rows: unsupported shape")
     x = x.contiguous()
     y = torch.empty(B, H // 2, W // 2, Cout, dtype=x.dtype, device=x.device)
-    yd = torch.empty_like(y)
-    wf, wdf = stream_weight_frag(w_packed), stream_weight_frag(wd_packed)
-    C.conv3x3_s2rows(_ptr(x), _ptr(wf), _ptr(bias.float().contiguous()), _ptr(wdf), _ptr(bd.float().contiguous()),
-                     _ptr(y), _ptr(yd), _ptr(_zero_page(x.device)), B, relu, _stream())
-    return y, yd
+    yd = torch.empty_like(y) if wd_packed is not None else None
+    wf = stream_weight_frag(w_packed)
+    wdf = stream_weight_frag(wd_packed) if wd_packed is not None else None
+    C.conv3x3_s2rows(_ptr(x), _ptr(wf), _ptr(bias.float().contiguous()), _ptr(wdf),
+                     _ptr(None if bd is None else bd.float().contiguous()), _ptr(y), _ptr(yd),
+                     _ptr(_zero_page(x.device)), B, relu, _stream())
+    return y if wd_packed is None else (y, yd)
 
 
 def conv3x3_s2rows128(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, relu: bool = True,
@@ -293,10 +299,17 @@ def conv_small(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, res:
 
 
 def conv3x3_rows28(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, res: torch.Tensor | None = None,
-                   relu: bool = True) -> torch.Tensor:
+                   relu: bool = True, downsample: tuple | None = None, out_inv_scale: float = 0.0) -> torch.Tensor:
     """Weight-stationary row-streaming 3x3/s1/p1 conv on [B,28,28,128] ->
     128 channels (conv3x3_rows28.hip): relu?(conv(x) + bias (+ res)).
-    w_packed: conv2d packed weights [128, 1152]."""
+    w_packed: conv2d packed weights [128, 1152].
+
+    downsample=(x56 [B,56,56,64], wd_packed [128, 64], bd): the block's 1x1/s2
+    downsample of x56 as 2 more K steps of this conv, in place of a residual:
+    relu?(conv(x) + bias + conv1x1_s2(x56) + bd).
+
+    out_inv_scale > 0: returns e4m3 bytes (uint8) of relu?(conv(x) + bias) *
+    out_inv_scale; no residual and no downsample with it."""
     _need_cuda(x, w_packed, bias, res)
     C = native()
     B, H, W, Cin = x.shape
@@ -305,10 +318,23 @@ def conv3x3_rows28(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, 
         raise ValueError("conv3x3_rows28: unsupported shape")
     if res is not None and tuple(res.shape) != (B, H, W, Cout):
         raise ValueError("conv3x3_rows28: residual shape")
+    if out_inv_scale > 0 and (res is not None or downsample is not None):
+        raise ValueError("conv3x3_rows28: e4m3 output takes neither a residual nor a downsample")
     x = x.contiguous()
-    y = torch.empty_like(x)
+    xds = wds = bds = None
+    if downsample is not None:
+        if res is not None:
+            raise ValueError("conv3x3_rows28: the downsample takes the residual's place")
+        x56, wd_packed, bd = downsample
+        _need_cuda(x56, wd_packed, bd)
+        if tuple(x56.shape) != (B, 2 * H, 2 * W, Cin // 2) or x56.dtype != x.dtype \
+                or tuple(wd_packed.shape) != (Cout, Cin // 2) or bd.numel() != Cout:
+            raise ValueError("conv3x3_rows28: downsample needs x56 [B, 56, 56, 64], wd_packed [128, 64], bd [128]")
+        xds, wds, bds = x56.contiguous(), stream_weight_frag(wd_packed), bd.float().contiguous()
+    y = torch.empty(B, H, W, Cout, dtype=torch.uint8 if out_inv_scale > 0 else x.dtype, device=x.device)
     C.conv3x3_rows28(_ptr(x), _ptr(stream_weight_frag(w_packed)), _ptr(bias.float().contiguous()),
-                     _ptr(None if res is None else res.contiguous()), _ptr(y), B, relu, _stream())
+                     _ptr(None if res is None else res.contiguous()), _ptr(y), B, relu, _stream(),
+                     float(out_inv_scale), _ptr(xds), _ptr(wds), _ptr(bds))
     return y
 
 

@@ -412,8 +412,9 @@ def test_fused_block_matches_unfused(gpu):
     row convs per block (options fused_block=False): same MFMA order and bf16
     intermediate; the fused block starts its accumulators from the bias and
     adds the residual by v_dot2c_f32_bf16 (rounding differently from the row
-    convs' bias-after / unpacked-residual epilogue, which the kernel test pins
-    bit for bit as variant 32), so the logits agree to bf16 rounding."""
+    convs' bias-after / unpacked-residual epilogue; the op tests hold both to
+    the same float64 bar, test_kernels_resnet_gpu.py), so the logits agree to
+    bf16 rounding."""
     model = build("resnet18", seed=43, randomize_bn=True)
     sd = state_dict_f32(model)
     g = torch.Generator().manual_seed(44)

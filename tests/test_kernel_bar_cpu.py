@@ -3,6 +3,7 @@ rounded to bf16 (what a correct kernel may return at worst, to first order)
 passes against itself, and each modelled kernel fault is rejected."""
 import pytest
 import torch
+import torch.nn.functional as F
 
 import _kernel_bar as kb
 
@@ -91,3 +92,111 @@ def test_avgpool_bar_and_control():
     wrong = kb.nhwc(torch.relu(kb.fault_border_taps(ref, x, w, 1))).reshape(3, 49, 512)
     kb.assert_rejects(got, wrong.mean(1), bnd, "border")
     kb.assert_rejects(got, y[:, :48].sum(1) / 49, bnd, "last pixel left out")
+
+
+def test_padded_pool_bar_and_controls():
+    """The ResNet stem's pool (3x3/s2/p1) after a 7x7/s2/p3 conv + ReLU: -inf
+    and zero padding agree, an fp32 conv rounded to bf16 and pooled passes,
+    the faults do not."""
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(2, 3, 64, 64, generator=g).bfloat16().double()
+    w = (torch.randn(64, 3, 7, 7, generator=g) / 147 ** 0.5).bfloat16().double()
+    bias = (torch.randn(64, generator=g) * 0.1).double()
+    ref, mag = kb.conv_ref(x, w, bias, 2, 3)
+    r = torch.relu(ref)
+    assert torch.equal(kb.maxpool(r, pad=1), F.max_pool2d(F.pad(r, (1, 1, 1, 1)), 3, 2))
+    cb = kb.bound(r, mag, 147)
+    got = kb.maxpool(kb.bf16r(torch.relu(F.conv2d(x.float(), w.float(), bias.float(), 2, 3))), pad=1)
+    assert got.shape == (2, 64, 16, 16)
+    kb.assert_close_pooled(got, r, cb, "clean", pad=1)
+    lost = F.conv2d(x[:, :, 0:1, :], w[:, :, 1:2, :], None, (1, 2), (0, 3))  # conv row 1 loses its taps on image row 0
+    wrong = ref.clone()
+    wrong[:, :, 1:2, :] -= lost
+    for name, wr in (("border", wrong), ("swap", kb.fault_chunk_swap_at_max(ref)), ("batch", kb.fault_batch_shift(ref))):
+        kb.assert_rejects(got, kb.maxpool(torch.relu(wr), pad=1), kb.maxpool(cb, pad=1), name)
+
+
+def _block_fp32(x, w1, b1, w2, b2):
+    """The block as a kernel computes it: fp32 convs, a bf16 intermediate, a
+    bf16 output."""
+    t = torch.relu(F.conv2d(x.float(), w1.float(), b1.float(), 1, 1)).bfloat16().float()
+    return kb.bf16r(torch.relu(F.conv2d(t, w2.float(), b2.float(), 1, 1) + x.float()))
+
+
+def test_chained_bar_and_controls():
+    ring = kb.kernel_const("conv3x3_block.hip", "kRing")
+    ops5 = kb.block_operands(2, seed=6)
+    ref, bnd, delta, _ = kb.chained(*ops5)
+    got = _block_fp32(*ops5)
+    kb.assert_close(got, torch.relu(ref), bnd, "clean")
+    assert 0 < (delta > 0).double().mean().item() < 0.5  # the intermediate is known exactly on most elements
+    for name, wrong in kb.block_controls(*ops5, ring):
+        kb.assert_rejects(got, torch.relu(wrong), bnd, name)
+
+
+@pytest.mark.parametrize("B", [1, 3])
+def test_chained_bar_is_not_swamped(B):
+    """A condition on the GPU test's own operands (test_kernels_resnet_gpu.py,
+    seed 130 + B): the delta term leaves every control above the bar."""
+    ring = kb.kernel_const("conv3x3_block.hip", "kRing")
+    ops5 = kb.block_operands(B, seed=130 + B)
+    ref, bnd, delta, _ = kb.chained(*ops5)
+    share = (F.conv2d(delta, ops5[3].abs(), None, 1, 1) / bnd).max().item()
+    got = _block_fp32(*ops5)
+    ratios = [kb.worst(got, torch.relu(wrong), bnd)[0] for _, wrong in kb.block_controls(*ops5, ring)]
+    print(f"block B={B}: delta term at most {share:.2f} of the bar, smallest control ratio {min(ratios):.1f}")
+    assert min(ratios) > 1.0, ratios
+
+
+def test_e4m3_bar_and_controls():
+    x, w, bias = _conv_case(2, 128, 128, 28, 3, 1, seed=7)
+    ref, mag = kb.conv_ref(x, w, bias, 1, 1)
+    r = torch.relu(ref)
+    inv = 400.0 / r.max().item()
+    bnd = kb.e4m3_bound(r, mag, 1152, inv)
+    q = lambda t: (t * inv).float().to(torch.float8_e4m3fn).double()
+    got = q(torch.relu(F.conv2d(x.float(), w.float(), bias.float(), 1, 1)).double())
+    assert bool(((r * inv > 0) & (r * inv < 2.0 ** -6)).any()), "no value in the subnormal range"
+    ratio, _ = kb.assert_close(got, r * inv, bnd, "clean", l2=4e-2)
+    assert ratio > 0.5  # the bar is e4m3's own roundoff, not a loose multiple of it
+    for name, wrong in (("border", kb.fault_border_taps(ref, x, w, 1)), ("swap", kb.fault_chunk_swap(ref)),
+                        ("batch", kb.fault_batch_shift(ref)),
+                        ("ring", kb.fault_ring_row(ref, x, w, 9, kb.kernel_const("conv3x3_rows28.hip", "kRing")))):
+        kb.assert_rejects(got, torch.relu(wrong) * inv, bnd, name)
+    with pytest.raises(AssertionError):
+        kb.e4m3_bound(r, mag, 1152, 500.0 / r.max().item())
+
+
+def test_strided_and_downsample_faults():
+    """fault_ring_row and fault_strided_parity on a stride-2 conv, and
+    fault_ds_missing / fault_strided_parity on a conv that takes the 1x1/s2
+    downsample as extra K steps: the clean result passes, each fault does not."""
+    g = torch.Generator().manual_seed(8)
+    x56 = torch.randn(2, 64, 56, 56, generator=g).bfloat16().double()
+    w = (torch.randn(128, 64, 3, 3, generator=g) / 24).bfloat16().double()
+    bias = (torch.randn(128, generator=g) * 0.1).double()
+    ref, mag = kb.conv_ref(x56, w, bias, 2, 1)
+    bnd = kb.bound(torch.relu(ref), mag, 576)
+    got = kb.bf16r(torch.relu(ref))
+    kb.assert_close(got, torch.relu(ref), bnd, "s2 clean")
+    ring = kb.kernel_const("conv3x3_s2rows.hip", "kRing")
+    wrong = kb.fault_ring_row(ref, x56, w, 9, ring, stride=2)
+    assert torch.equal(wrong[:, :, :9], ref[:, :, :9]) and torch.equal(wrong[:, :, 10:], ref[:, :, 10:])
+    kb.assert_rejects(got, torch.relu(wrong), bnd, "ring row")
+    wrong = kb.fault_strided_parity(ref, x56, w, 13, 1)
+    shifted = F.conv2d(torch.roll(x56, -1, 3), w, bias, 2, 1)  # (column 13's taps stay clear of the wrapped column)
+    assert torch.allclose(wrong[..., 13], shifted[..., 13], rtol=0, atol=1e-12)
+    assert torch.equal(wrong[..., :13], ref[..., :13])
+    kb.assert_rejects(got, torch.relu(wrong), bnd, "parity")
+    # the block's conv2 with the downsample as 2 more K steps
+    x, w2, b2 = _conv_case(2, 128, 128, 28, 3, 1, seed=9)
+    wd = (torch.randn(128, 64, 1, 1, generator=g) / 8).bfloat16().double()
+    bd = (torch.randn(128, generator=g) * 0.1).double()
+    c, cm = kb.conv_ref(x, w2, b2, 1, 1)
+    d, dm = kb.conv_ref(x56, wd, bd, 2, 0)
+    ref, mag = c + d, cm + dm
+    bnd = kb.bound(torch.relu(ref), mag, 1216)
+    got = kb.bf16r(torch.relu(ref))
+    kb.assert_close(got, torch.relu(ref), bnd, "conv + downsample clean")
+    kb.assert_rejects(got, torch.relu(kb.fault_ds_missing(ref, x56, wd, b=1, frag=48)), bnd, "ds missing")
+    kb.assert_rejects(got, torch.relu(kb.fault_strided_parity(ref, x56, wd, 27, 0)), bnd, "ds parity")
