@@ -13,8 +13,10 @@
 //    step from a 10-row LDS-DMA ring of x (the conv3x3_rows layout: 58 staged
 //    columns with zero pads, 16-B chunks XOR-swizzled by column), written as
 //    bf16 into a 10-row LDS ring of t with the same layout;
-//  * waves 4-7 CONSUME it: conv2 over t rows + b2 + residual (x rows re-read
-//    from L2/MALL: they were DMA'd a few steps earlier) + ReLU -> y.
+//  * waves 4-7 CONSUME it: conv2 over t rows + b2 + residual + ReLU -> y. The
+//    residual rows are still in the x ring one step before they are needed
+//    (its oldest four rows): the consumers read them from there into
+//    registers, so x leaves memory once.
 //  Producer wave w and consumer wave w+4 share SIMD w: matrix work of both
 //  roles interleaves on every SIMD. Each role's 4 waves = 2 pixel halves (2
 //  rows x 56 = 7 fragments of 16 pixels) x 2 channel halves (2 N fragments),
@@ -71,7 +73,8 @@ constexpr int kSteps = kH / kR + 2;    // 16
 // retires in order: a weight load issued after the DMA cannot be waited on
 // without waiting for the DMA too).
 template <bool PROD, int PD, int DMA_KS>
-__device__ __forceinline__ void block_role(const BlockArgs& a, char* xring, char* tring, int rw, int lane) {
+__device__ __forceinline__ void block_role(const BlockArgs& a, char* xring, char* tring, const float* biasl, int rw,
+                                           int lane) {
   const int wm = rw & 1, wn = rw >> 1;
   const int fr = lane & 15, g = lane >> 4;
   const int b = blockIdx.x;
@@ -136,19 +139,21 @@ __device__ __forceinline__ void block_role(const BlockArgs& a, char* xring, char
   for (int ks = 0; ks < PD - 1; ++ks)
 #pragma unroll
     for (int nf = 0; nf < 2; ++nf) wq[ks][nf] = wload(ks * 2 + nf);
-  // this lane's 8 output channels: wn*32 + 8g .. +7 (weight rows permuted, perm32)
-  const float* bias = PROD ? a.bias1 : a.bias2;
-  float bs[2][4];
-#pragma unroll
-  for (int nf = 0; nf < 2; ++nf)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) bs[nf][i] = bias[wn * 32 + 8 * g + 4 * nf + i];
+  // this lane's 8 output channels: wn*32 + 8g .. +7 (weight rows permuted,
+  // perm32). Their biases are re-read from LDS at the top of every step (the
+  // kernel's prologue put both convs' there): they are needed by the first K
+  // step only, and 8 registers held over the K loop are 8 too many next to
+  // the residual's 28.
+  const floatx4* bias = (const floatx4*)(biasl + (PROD ? 0 : kC) + wn * 32 + 8 * g);
 
   vm_wait<0>();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
   const char* src_ring = PROD ? xring : tring;
+  // consumer: the residual (x rows base .. base + 3 of its step), read from
+  // the x ring at the end of the step before (below)
+  uint4 rres[PROD ? 1 : kMF];
   for (int step = 0; step < kSteps; ++step) {
     // producer: t rows base..base+3 = P_{step-1} (step 0: base -3, only rows
     // -1, 0 = pixel half 1); consumer: y rows base..base+3 = C_{step-2}
@@ -172,21 +177,11 @@ __device__ __forceinline__ void block_role(const BlockArgs& a, char* xring, char
       const int rs0 = (rb % kRing) * kSlot, rs1 = ((rb + 1) % kRing) * kSlot;
       const int rs2 = ((rb + 2) % kRing) * kSlot, rs3 = ((rb + 3) % kRing) * kSlot;
       auto rsl = [&](int j) __attribute__((always_inline)) { return j == 0 ? rs0 : j == 1 ? rs1 : j == 2 ? rs2 : rs3; };
-      // consumer: residual rows (x), loaded now so they land during the MFMAs
       const long obase = ((long)b * kH + base) * kW * kC;
-      uint4 rres[PROD ? 1 : kMF];
-      if constexpr (!PROD) {
-#pragma unroll
-        for (int f = 0; f < kMF; ++f) {
-          const int p = wm * (kR * kW / 2) + 16 * f + fr;
-          rres[f] = *(const uint4*)(a.x + obase + (long)p * kC + wn * 32 + 8 * g);
-        }
-      }
       floatx4 acc[kMF][2];
       // the bias is the first MFMA's accumulator input (no zeroing, no bias
       // adds in the epilogue)
-      const floatx4 bv[2] = {floatx4{bs[0][0], bs[0][1], bs[0][2], bs[0][3]},
-                             floatx4{bs[1][0], bs[1][1], bs[1][2], bs[1][3]}};
+      const floatx4 bv[2] = {bias[0], bias[1]};
       bf16x8 xc[kMF], xn[kMF];
       auto load_k = [&](int ks, bf16x8* xd) __attribute__((always_inline)) {
         const int tap = ks >> 1, h = ks & 1;
@@ -262,6 +257,22 @@ __device__ __forceinline__ void block_role(const BlockArgs& a, char* xring, char
         }
       }
     }
+    // consumer: the next step's residual = x rows nb .. nb + 3, nb = 4 (step - 1).
+    // They are the oldest four rows of the x ring (it holds rows nb .. nb + 9
+    // in this step) and the next step's DMA overwrites them, so they are read
+    // here, before the barrier that the DMA is issued behind, and kept in
+    // registers over the next step's K loop: no second read of x from memory.
+    // Lane (f, fr, g) wants channels 32 wn + 8 g .. + 7 of its pixel: the
+    // centre tap's fragment of K half wn (the address of load_k's kw = 1 read).
+    if constexpr (!PROD) {
+      if (step >= 1 && step + 1 < kSteps) {
+        const int nr = 4 * (step - 1) + 2 * wm;
+        const int ns0 = (nr % kRing) * kSlot + wn * kHalf, ns1 = ((nr + 1) % kRing) * kSlot + wn * kHalf;
+#pragma unroll
+        for (int f = 0; f < kMF; ++f)
+          rres[f] = *(const uint4*)(xring + (((hi1 >> f) & 1) ? ns1 : ns0) + colq[f][1]);
+      }
+    }
     // (an idle role's weight ring needs nothing: it is periodic over K steps)
     // t rows written and the next step's x rows landed, for every wave
     if constexpr (PROD) vm_wait<0>();
@@ -281,12 +292,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_block_kernel(BlockArgs a) {
   // zero both rings (pad columns stay zero; x row -1 is the zeroed slot 9;
   // t halo rows are written as zeros), before any x-row DMA lands
   for (int i = tid; i < 2 * kRing * kSlot / 16; i += 512) ((uint4*)xring)[i] = make_uint4(0, 0, 0, 0);
+  // both convs' biases behind the rings: [2][64] floats
+  float* biasl = (float*)(tring + kRing * kSlot);
+  if (tid < 2 * kC) biasl[tid] = tid < kC ? a.bias1[tid] : a.bias2[tid - kC];
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   if (wave < 4)
-    block_role<true, PD, DMA_KS>(a, xring, tring, wave & 3, lane);
+    block_role<true, PD, DMA_KS>(a, xring, tring, biasl, wave & 3, lane);
   else
-    block_role<false, PD, DMA_KS>(a, xring, tring, wave & 3, lane);
+    block_role<false, PD, DMA_KS>(a, xring, tring, biasl, wave & 3, lane);
 }
 
 }  // namespace
@@ -309,7 +323,7 @@ void conv3x3_block(const void* x, const void* wf1, const float* bias1, const voi
   a.y = (bf16*)y;
   a.zero = (const bf16*)zero;
   a.stagger = kernel_stagger(kStagBlock);
-  const size_t lds = (size_t)2 * kRing * kSlot;  // 148.5 KB
+  const size_t lds = (size_t)2 * kRing * kSlot + 2 * kC * sizeof(float);  // 149.0 KB: two rings, the biases
   // PD 6: 5 K steps of weight lookahead (PD 3 and a mid-step DMA measured
   // the same, 116-120 us at B=256); tools/block_bench.py
   hipLaunchKernelGGL((conv3x3_block_kernel<6, 0>), dim3(B), dim3(512), lds, s, a);

@@ -1,6 +1,9 @@
 // Direct 3x3 / pad 1 convolution (stride 1 or 2) with the input image resident
-// in LDS, BN folded, optional residual, ReLU. ResNet18 at batch >= 32 runs
-// every 3x3 conv from layer2 on through it:
+// in LDS, BN folded, optional residual, ReLU. It can run every 3x3 conv of
+// ResNet18 from layer2 on; at batches that fill the GPU one image per CU the
+// default plan gives layer2 to conv3x3_s2rows (layer2.0.conv1 + downsample) and
+// conv3x3_rows28 (its stride-1 convs) and runs layer3 and layer4 through this
+// kernel. The shapes:
 //   stride 1: layer2 (28x28x128), layer3 (14x14x256), layer4 (7x7x512)
 //   stride 2: layer2.0.conv1 (56x56x64 -> 28x28x128), layer3.0.conv1 (28x28x128
 //             -> 14x14x256), layer4.0.conv1 (14x14x256 -> 7x7x512); these also
