@@ -458,6 +458,12 @@ PYBIND11_MODULE(_C, m) {
     softmax_topk(P<float>(logits), B, N, ld, k, P<int32_t>(idx), P<float>(prob), S(stream));
   }, py::arg("logits"), py::arg("B"), py::arg("N"), py::arg("ld"), py::arg("k"), py::arg("idx"), py::arg("prob"),
         py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("embed_rows_supported", &embed_rows_supported, py::arg("HW"), py::arg("C"));
+  m.def("embed_rows", [](uintptr_t x, uintptr_t out, int B, int HW, int C, bool in_fp8, float scale, bool l2norm,
+                         uintptr_t stream) {
+    embed_rows(P<void>(x), P<float>(out), B, HW, C, in_fp8, scale, l2norm, S(stream));
+  }, py::arg("x"), py::arg("out"), py::arg("B"), py::arg("HW"), py::arg("C"), py::arg("in_fp8"), py::arg("scale"),
+        py::arg("l2norm"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
 
   // ---------------------------------------------------------------- jpeg
   m.def("decode_jpeg", [](py::bytes data) {
@@ -614,14 +620,14 @@ PYBIND11_MODULE(_C, m) {
   };
   m.def("plan_audit", [=](const std::string& arch, const py::dict& weights, const std::map<std::string, bool>& options,
                           int B, bool native, int num_cus, int num_classes, int image_size, int topk,
-                          bool tensor_in) {
+                          bool tensor_in, bool features) {
     std::vector<Op> ops;
     const auto lines = Engine::plan_audit(arch, to_weight_map(weights), engine_options(options), B, native, num_cus,
-                                          &ops, num_classes, image_size, topk, tensor_in);
+                                          &ops, num_classes, image_size, topk, tensor_in, features);
     return py::make_tuple(plan_list(lines), op_list(ops));
   }, py::arg("arch"), py::arg("weights"), py::arg("options") = std::map<std::string, bool>{}, py::arg("B") = 256,
      py::arg("native") = true, py::arg("num_cus") = 256, py::arg("num_classes") = 1000, py::arg("image_size") = 224,
-     py::arg("topk") = 1, py::arg("tensor_in") = false);
+     py::arg("topk") = 1, py::arg("tensor_in") = false, py::arg("features") = false);
   py::class_<Engine>(m, "Engine")
       .def(py::init([](const std::string& arch, const py::dict& weights, int device, int num_classes,
                        int image_size, const std::map<std::string, bool>& options) {
@@ -651,22 +657,24 @@ PYBIND11_MODULE(_C, m) {
       .def(
           "forward_topk",
           [](Engine& e, uintptr_t images, int B, int Hin, int Win, int k, uintptr_t idx, uintptr_t prob,
-             uintptr_t logits, uintptr_t stream, bool use_graph) {
+             uintptr_t logits, uintptr_t stream, bool use_graph, uintptr_t features, bool l2norm) {
             e.forward_topk(P<uint8_t>(images), B, Hin, Win, k, P<int32_t>(idx), P<float>(prob), P<float>(logits),
-                           S(stream), use_graph);
+                           S(stream), use_graph, P<float>(features), l2norm);
           },
           py::arg("images"), py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("k"), py::arg("idx"),
           py::arg("prob"), py::arg("logits"), py::arg("stream"), py::arg("use_graph") = true,
+          py::arg("features") = (uintptr_t)0, py::arg("l2norm") = false,
           py::call_guard<py::gil_scoped_release>())
       .def(
           "forward_tensor",
           [](Engine& e, uintptr_t x, TensorDType dt, bool channels_last, int B, int k, uintptr_t idx, uintptr_t prob,
-             uintptr_t logits, uintptr_t stream, bool use_graph) {
+             uintptr_t logits, uintptr_t stream, bool use_graph, uintptr_t features, bool l2norm) {
             e.forward_tensor(P<void>(x), dt, channels_last, B, k, P<int32_t>(idx), P<float>(prob), P<float>(logits),
-                             S(stream), use_graph);
+                             S(stream), use_graph, P<float>(features), l2norm);
           },
           py::arg("x"), py::arg("dtype"), py::arg("channels_last"), py::arg("B"), py::arg("k"), py::arg("idx"),
           py::arg("prob"), py::arg("logits"), py::arg("stream"), py::arg("use_graph") = true,
+          py::arg("features") = (uintptr_t)0, py::arg("l2norm") = false,
           py::call_guard<py::gil_scoped_release>())
       .def("profile",
            [](Engine& e, uintptr_t images, int B, int Hin, int Win, uintptr_t stream) {
@@ -679,9 +687,25 @@ PYBIND11_MODULE(_C, m) {
              return py::make_tuple(s.H, s.W, s.C, s.f32);
            })
       .def("op_list", [=](const Engine& e) { return op_list(e.ops()); })
-      .def("plan", [=](const Engine& e, int B, int Hin, int Win, int topk, bool tensor_in) {
-        return plan_list(e.plan_lines(e.plan(B, Hin, Win, topk, tensor_in)));
-      }, py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("topk") = 1, py::arg("tensor_in") = false)
+      // the first B images of a stored activation, copied to dst (device, B * H * W * C elements) on `stream`
+      .def("read_activation",
+           [](const Engine& e, int id, int B, uintptr_t dst, uintptr_t stream) {
+             const ActShape s = e.activation_shape(id);
+             if (B < 0 || B > e.max_batch()) throw std::invalid_argument("read_activation: B outside 0..max_batch");
+             DMLC_HIP_CHECK(hipMemcpyAsync(P<void>(dst), e.activation(id), (size_t)B * s.elems_per_image() * s.elem_bytes(),
+                                           hipMemcpyDeviceToDevice, S(stream)));
+           })
+      // (e4m3, per-tensor scale) of a stored activation
+      .def("activation_quant",
+           [](const Engine& e, int id) {
+             auto s = e.activation_shape(id);
+             return py::make_tuple(s.fp8, s.scale);
+           })
+      .def("plan", [=](const Engine& e, int B, int Hin, int Win, int topk, bool tensor_in, bool features) {
+        return plan_list(e.plan_lines(e.plan(B, Hin, Win, topk, tensor_in, features)));
+      }, py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("topk") = 1, py::arg("tensor_in") = false,
+         py::arg("features") = false)
+      .def_property_readonly("feature_dim", &Engine::feature_dim)
       .def_property_readonly("num_cus", &Engine::num_cus)
       .def_property_readonly("num_activations", &Engine::num_activations)
       .def_property_readonly("arch", &Engine::arch)

@@ -448,4 +448,15 @@ constexpr int kMaxTopK = 16;
 void softmax_topk(const float* logits, int B, int N, int ld, int k, int32_t* idx /*[B,k]*/, float* prob /*[B,k]*/,
                   hipStream_t s);
 
+// The vector a classifier reads, as fp32 rows (embed.hip): x is [B, HW, C]
+// bf16, or e4m3 with a per-tensor `scale` (HW > 1 only); out is fp32 [B, C],
+// dense. HW == 1: the bf16 element widened (exact). HW > 1: avgpool_global's
+// average, bit for bit (its summation order, one multiply by (in_fp8 ? scale
+// : 1) / HW, rounded to bf16, widened). l2norm: every row divided by
+// max(sqrt(sum_c v^2), 1e-12), torch's F.normalize; an all-zero row stays
+// zero. x needs 16-B alignment (8-B for e4m3) and out 16-B.
+bool embed_rows_supported(int HW, int C);  // HW >= 1, C % 8 == 0, C <= 8192
+void embed_rows(const void* x, float* out, int B, int HW, int C, bool in_fp8, float scale, bool l2norm,
+                hipStream_t s);
+
 }  // namespace dmlc

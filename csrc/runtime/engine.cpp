@@ -163,12 +163,12 @@ std::vector<PackRegion> Engine::pack_audit(const std::string& arch, const Weight
 std::vector<Engine::PlanLine> Engine::plan_audit(const std::string& arch, const WeightMap& weights,
                                                  const EngineOptions& options, int B, bool native, int num_cus,
                                                  std::vector<Op>* engine_ops, int num_classes, int image_size,
-                                                 int topk, bool tensor_in) {
+                                                 int topk, bool tensor_in, bool features) {
   Engine e(HostOnly{}, arch, weights, num_classes, image_size, options);
   e.num_cus_ = num_cus;
   e.layout_weights();
   if (engine_ops) *engine_ops = e.ops_;
-  return e.plan_lines(e.plan(B, native, options.fork_ds, false, topk, tensor_in));
+  return e.plan_lines(e.plan(B, native, options.fork_ds, false, topk, tensor_in, features));
 }
 
 // Same graph, packing and calibration as `src`, on another device, with an
@@ -930,8 +930,8 @@ const char* kernel_name(Kernel k) {
       "None", "AlexStem", "StemPoolU8", "StemPool", "FcSmall", "Conv1x1Cat", "Conv1x1Chain", "Bottleneck56",
       "Bottleneck56Head", "Block", "S2Rows", "S2Rows128", "Stream", "Stream8", "Rows28", "Rows", "Small", "Direct13",
       "Direct27", "Conv1x1", "BigTile", "Igemm", "FcGemm", "HeadPooled", "HeadFused", "AvgPoolGlobal",
-      "AvgPoolAdaptive", "MaxPool", "Preprocess", "PackTensor", "SoftmaxTop1", "SoftmaxTopK"};
-  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::SoftmaxTopK + 1, "one name per Kernel");
+      "AvgPoolAdaptive", "MaxPool", "Preprocess", "PackTensor", "SoftmaxTop1", "SoftmaxTopK", "Embed"};
+  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::Embed + 1, "one name per Kernel");
   return names[(size_t)k];
 }
 
@@ -1347,7 +1347,63 @@ struct Engine::Planner {
     }
   }
 
-  std::vector<Step> run(bool native, bool side, bool keep_acts, int topk, bool tensor_in) {
+  // the step that does op oi (a launch, or None for an op another step computes)
+  const Step& step_of(int oi) const {
+    for (const Step& st : steps)
+      if (st.n_ops > 0 && st.first_op <= oi && oi < st.first_op + st.n_ops) return st;
+    throw std::logic_error("plan: no step for op " + ops[oi].name);
+  }
+  // Op oi's output activation is known to be in memory after the plan's
+  // steps: a conv's epilogue pooled into it, or it is the last op of a launch
+  // that stores its output (an inner op's may stay on chip: HeadFused's pooled
+  // vector, a fused block's intermediate).
+  bool stored(int oi) const {
+    for (const Step& st : steps)
+      if (st.pool_op == oi) return true;
+    const Step& st = step_of(oi);
+    return st.kernel != Kernel::None && oi == st.first_op + st.n_ops - 1 && st.store_y;
+  }
+
+  // The Embed step (header: Engine::plan). F = the input of the fc that
+  // writes the logits.
+  void plan_embed() {
+    int fc = -1;
+    for (size_t i = 0; i < ops.size(); ++i)
+      if (ops[i].type == OpType::Conv && ops[i].out == e.logits_act_) fc = (int)i;
+    if (fc < 0) throw std::logic_error("features: no fc writes the logits");
+    int prod = -1;  // the op that writes F
+    for (size_t i = 0; i < ops.size(); ++i)
+      if (ops[i].out == ops[fc].in) prod = (int)i;
+    if (prod < 0) throw std::logic_error("features: nothing writes the fc's input");
+    Step st;
+    st.kernel = Kernel::Embed;
+    st.first_op = (int)ops.size() - 1;
+    st.n_ops = 0;
+    const ActShape& fs = shapes[ops[prod].out];
+    if (stored(prod)) {
+      if (fs.f32 || fs.fp8 || !embed_rows_supported(1, (int)fs.elems_per_image()))
+        throw std::logic_error("features: the fc's input is no bf16 row embed_rows reads");
+      st.src_op = prod;
+    } else {
+      // only HeadFused leaves F unwritten; it pools ops[prod].in, which a step
+      // stores (store_y is false only where the pool is fused, and then F exists)
+      const Op& pool = ops[prod];
+      if (step_of(prod).kernel != Kernel::HeadFused || pool.type != OpType::AvgPoolGlobal)
+        throw std::logic_error("features: the fc's input is not stored and no fused head pools it");
+      int src = -1;
+      for (size_t i = 0; i < ops.size(); ++i)
+        if (ops[i].out == pool.in) src = (int)i;
+      const ActShape& is = shapes[pool.in];
+      if (src < 0 || !stored(src)) throw std::logic_error("features: the fused head's input is not stored");
+      if (is.f32 || !is.cscale.empty() || is.H * is.W < 2 || !embed_rows_supported(is.H * is.W, is.C))
+        throw std::logic_error("features: embed_rows cannot pool the fused head's input");
+      st.src_op = src;
+      st.count = is.H * is.W;
+    }
+    steps.push_back(st);
+  }
+
+  std::vector<Step> run(bool native, bool side, bool keep_acts, int topk, bool tensor_in, bool features) {
     // a float tensor takes the resized-input plan: the u8 stems cannot read it
     if (tensor_in) native = false;
     // never a side stream next to a big-tile conv
@@ -1414,14 +1470,23 @@ struct Engine::Planner {
       Step& st = emit(Kernel::SoftmaxTopK, ops.size() - 1, 0);
       st.count = topk;
     }
+    // features: the plan above unchanged, then the fc's input as fp32 rows
+    if (features) plan_embed();
     return std::move(steps);
   }
 };
 
-std::vector<Step> Engine::plan(int B, bool native, bool side, bool keep_acts, int topk, bool tensor_in) const {
+std::vector<Step> Engine::plan(int B, bool native, bool side, bool keep_acts, int topk, bool tensor_in,
+                               bool features) const {
   if (topk < 1 || topk > std::min(num_classes_, kMaxTopK))
     throw std::invalid_argument("top-k: k must be in 1..min(num_classes, " + std::to_string(kMaxTopK) + ")");
-  return Planner(*this, B).run(native, side, keep_acts, topk, tensor_in);
+  return Planner(*this, B).run(native, side, keep_acts, topk, tensor_in, features);
+}
+
+int Engine::feature_dim() const {
+  for (const Op& op : ops_)
+    if (op.type == OpType::Conv && op.out == logits_act_) return convs_[op.conv].cin;
+  throw std::logic_error("feature_dim: no fc writes the logits");
 }
 
 std::string Engine::step_detail(const Step& st) const {
@@ -1430,12 +1495,13 @@ std::string Engine::step_detail(const Step& st) const {
   const bool in_k = st.kernel == Kernel::Rows28 || st.kernel == Kernel::Conv1x1Cat;  // no activation written
   if (st.ds_op >= 0) add((in_k ? "dsk=" : "ds=") + ops_[st.ds_op].name);
   if (st.pool_op >= 0) add("pool=" + ops_[st.pool_op].name);
+  if (st.src_op >= 0) add("in=" + ops_[st.src_op].name);
   if (st.wreg) add("wreg");
   if (!st.store_y) add("nostore");
   if (st.side) add("side");
   if (st.cfg >= 0) add("cfg=" + std::to_string(st.cfg));
   if (st.count > 0) {
-    const char* what = st.kernel == Kernel::Small ? "mf=" : st.kernel == Kernel::SoftmaxTopK ? "k=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm) ? "splits=" : "strip=";
+    const char* what = st.kernel == Kernel::Small ? "mf=" : st.kernel == Kernel::SoftmaxTopK ? "k=" : st.kernel == Kernel::Embed ? "hw=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm) ? "splits=" : "strip=";
     add(what + std::to_string(st.count));
   }
   return d;
@@ -1449,14 +1515,18 @@ std::vector<Engine::PlanLine> Engine::plan_lines(const std::vector<Step>& steps)
 
 // ---------------------------------------------------------------- executor
 void Engine::run_ops(const std::vector<Step>& steps, const Input& in, int B, int32_t* idx, float* prob,
-                     float* logits, hipStream_t s, std::vector<hipEvent_t>* evs, bool trace) {
+                     float* logits, hipStream_t s, std::vector<hipEvent_t>* evs, bool trace, float* features,
+                     bool l2norm) {
   // the u8 kernels and PackTensor each read their own kind of input: a plan
   // made for the other kind is refused before anything is launched
   for (const Step& st : steps) {
     const bool u8 = st.kernel == Kernel::AlexStem || st.kernel == Kernel::Preprocess || st.kernel == Kernel::StemPoolU8;
     if ((u8 && in.tensor) || (st.kernel == Kernel::PackTensor && !in.tensor))
       throw std::logic_error(std::string("plan step ") + kernel_name(st.kernel) + " does not read this input");
+    if (st.kernel == Kernel::Embed && !features) throw std::logic_error("plan step Embed without a features buffer");
   }
+  if (features && (steps.empty() || steps.back().kernel != Kernel::Embed))
+    throw std::logic_error("a features buffer needs a plan made with features");
   const uint8_t* const images = in.tensor ? nullptr : (const uint8_t*)in.data;
   const int Hin = in.Hin, Win = in.Win;
   size_t ei = 0;
@@ -1469,7 +1539,8 @@ void Engine::run_ops(const std::vector<Step>& steps, const Input& in, int B, int
   auto inv_scale = [&](int act) { return shapes_[act].fp8 ? 1.f / shapes_[act].scale : 0.f; };
   // the tail's top-1: the caller's buffers, or scratch when there are none or
   // when they are the [B, k] outputs of a final SoftmaxTopK step
-  const bool topk = !steps.empty() && steps.back().kernel == Kernel::SoftmaxTopK;
+  bool topk = false;
+  for (const Step& st : steps) topk |= st.kernel == Kernel::SoftmaxTopK;
   int32_t* const idx_out = (idx && !topk) ? idx : dummy_idx_;
   float* const prob_out = (prob && !topk) ? prob : (float*)(dummy_idx_ + max_batch_);
   for (const Step& st : steps) {
@@ -1672,6 +1743,15 @@ void Engine::run_ops(const std::vector<Step>& steps, const Input& in, int B, int
         softmax_topk(logits ? logits : (const float*)acts_[logits_act_], B, num_classes_, num_classes_, st.count, idx,
                      prob, s);
         break;
+      case Kernel::Embed: {  // the fc's input, or the fused head's pooled as the head pools it
+        const int src = ops_[st.src_op].out;
+        const ActShape& ss = shapes_[src];
+        if (st.count > 0)
+          embed_rows(acts_[src], features, B, st.count, ss.C, ss.fp8, ss.scale, l2norm, s);
+        else
+          embed_rows(acts_[src], features, B, 1, (int)ss.elems_per_image(), false, 1.f, l2norm, s);
+        break;
+      }
     }
     if (st.side) {
       DMLC_HIP_CHECK(hipEventRecord(join_evs_[oi], side_));
@@ -1687,16 +1767,17 @@ void Engine::forward(const uint8_t* images, int B, int Hin, int Win, int32_t* id
 }
 
 void Engine::forward_topk(const uint8_t* images, int B, int Hin, int Win, int k, int32_t* idx, float* prob,
-                          float* logits, hipStream_t stream, bool use_graph) {
+                          float* logits, hipStream_t stream, bool use_graph, float* features, bool l2norm) {
   Input in;
   in.data = images;
   in.Hin = Hin;
   in.Win = Win;
-  forward_input(in, B, k, idx, prob, logits, stream, use_graph);
+  forward_input(in, B, k, idx, prob, logits, stream, use_graph, features, l2norm);
 }
 
 void Engine::forward_tensor(const void* x, TensorDType dt, bool channels_last, int B, int k, int32_t* idx,
-                            float* prob, float* logits, hipStream_t stream, bool use_graph) {
+                            float* prob, float* logits, hipStream_t stream, bool use_graph, float* features,
+                            bool l2norm) {
   if (dt != TensorDType::F32 && dt != TensorDType::F16 && dt != TensorDType::BF16)
     throw std::invalid_argument("forward_tensor: unknown dtype");
   Input in;
@@ -1705,11 +1786,11 @@ void Engine::forward_tensor(const void* x, TensorDType dt, bool channels_last, i
   in.tensor = true;
   in.dt = dt;
   in.channels_last = channels_last;
-  forward_input(in, B, k, idx, prob, logits, stream, use_graph);
+  forward_input(in, B, k, idx, prob, logits, stream, use_graph, features, l2norm);
 }
 
 void Engine::forward_input(const Input& in, int B, int k, int32_t* idx, float* prob, float* logits,
-                           hipStream_t stream, bool use_graph) {
+                           hipStream_t stream, bool use_graph, float* features, bool l2norm) {
   if (B <= 0) return;
   if (k < 1 || k > std::min(num_classes_, kMaxTopK))
     throw std::invalid_argument("top-k: k must be in 1..min(num_classes, " + std::to_string(kMaxTopK) + ")");
@@ -1727,14 +1808,15 @@ void Engine::forward_input(const Input& in, int B, int k, int32_t* idx, float* p
     // engine's stream and back (two cross-stream waits cost ~40 us of idle
     // GPU between back-to-back forwards: profiles/r1_graph_gap.txt). The
     // engine's own stream is only used to capture.
-    GraphKey key{in.data, B, Hin, Win, idx, prob, logits, k, in.kind()};
+    // (the flag is keyed only next to a buffer: without one it changes nothing)
+    GraphKey key{in.data, B, Hin, Win, idx, prob, logits, k, in.kind(), features, features && l2norm ? 1 : 0};
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
-      const std::vector<Step> steps = plan(B, native, opt_.fork_ds, false, k, in.tensor);
+      const std::vector<Step> steps = plan(B, native, opt_.fork_ds, false, k, in.tensor, features != nullptr);
       DMLC_HIP_CHECK(hipStreamSynchronize(stream));
       hipGraph_t g;
       DMLC_HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-      run_ops(steps, in, B, idx, prob, logits, stream_, nullptr, false);
+      run_ops(steps, in, B, idx, prob, logits, stream_, nullptr, false, features, l2norm);
       DMLC_HIP_CHECK(hipStreamEndCapture(stream_, &g));
       hipGraphExec_t ex;
       DMLC_HIP_CHECK(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
@@ -1745,7 +1827,8 @@ void Engine::forward_input(const Input& in, int B, int k, int32_t* idx, float* p
     DMLC_HIP_CHECK(hipGraphLaunch(it->second, stream));
   } else {  // eager launches straight onto the caller's stream
     DMLC_TRACE("engine.forward");
-    run_ops(plan(B, native, opt_.fork_ds, true, k, in.tensor), in, B, idx, prob, logits, stream, nullptr, true);
+    run_ops(plan(B, native, opt_.fork_ds, true, k, in.tensor, features != nullptr), in, B, idx, prob, logits, stream,
+            nullptr, true, features, l2norm);
   }
   DMLC_HIP_CHECK(hipEventRecord(ev_out_, stream));
   last_stream_ = stream;

@@ -177,7 +177,8 @@ enum class Kernel {
   None,  // nothing to launch: the op is computed inside another step, or not needed
   AlexStem, StemPoolU8, StemPool, FcSmall, Conv1x1Cat, Conv1x1Chain, Bottleneck56, Bottleneck56Head, Block,
   S2Rows, S2Rows128, Stream, Stream8, Rows28, Rows, Small, Direct13, Direct27, Conv1x1, BigTile, Igemm, FcGemm,
-  HeadPooled, HeadFused, AvgPoolGlobal, AvgPoolAdaptive, MaxPool, Preprocess, PackTensor, SoftmaxTop1, SoftmaxTopK
+  HeadPooled, HeadFused, AvgPoolGlobal, AvgPoolAdaptive, MaxPool, Preprocess, PackTensor, SoftmaxTop1, SoftmaxTopK,
+  Embed
 };
 const char* kernel_name(Kernel k);
 
@@ -193,7 +194,10 @@ struct Step {
   bool store_y = true;   // false: the last op's activation is not written (Stream with the pool fused, under a graph)
   bool side = false;     // runs on the side stream (fork_ds)
   int cfg = -1;          // BigTile: tile config
-  int count = 0;         // Rows / StemPool / StemPoolU8: strip; Small: mf; BigTile / FcGemm: K splits; SoftmaxTopK: k
+  // Rows / StemPool / StemPoolU8: strip; Small: mf; BigTile / FcGemm: K splits; SoftmaxTopK: k;
+  // Embed: the pixels it averages (0: src_op's output is the feature row itself)
+  int count = 0;
+  int src_op = -1;       // Embed: the op whose output activation it reads
 };
 
 class Engine {
@@ -231,11 +235,18 @@ class Engine {
   // tensor_in (forward_tensor): the native = false plan step for step, with
   // PackTensor in place of Preprocess (the u8 stems never run; `native` is
   // not looked at).
-  std::vector<Step> plan(int B, bool native, bool side, bool keep_acts, int topk = 1, bool tensor_in = false) const;
+  // features (a forward with a features buffer): the same steps, then one
+  // Embed step (after SoftmaxTopK when there is one; last op, n_ops 0) that
+  // writes the fc's input F as fp32 rows. Where a step of the plan stores F
+  // (an AvgPoolGlobal step, a conv epilogue's pool_op, AlexNet's classifier.4)
+  // it reads F; where HeadFused covers the pool, F is never written, and it
+  // averages the pool's input (always stored then) exactly as the pool would.
+  std::vector<Step> plan(int B, bool native, bool side, bool keep_acts, int topk = 1, bool tensor_in = false,
+                         bool features = false) const;
   // The plan a graph-captured forward(B, Hin, Win) / forward_topk(.., topk) /
   // forward_tensor (tensor_in) runs.
-  std::vector<Step> plan(int B, int Hin, int Win, int topk = 1, bool tensor_in = false) const {
-    return plan(B, Hin == image_size_ && Win == image_size_, opt_.fork_ds, false, topk, tensor_in);
+  std::vector<Step> plan(int B, int Hin, int Win, int topk = 1, bool tensor_in = false, bool features = false) const {
+    return plan(B, Hin == image_size_ && Win == image_size_, opt_.fork_ds, false, topk, tensor_in, features);
   }
   // A step's extra fields as text, e.g. "ds=layer2.0.downsample.0 wreg".
   std::string step_detail(const Step& st) const;
@@ -250,7 +261,8 @@ class Engine {
   static std::vector<PlanLine> plan_audit(const std::string& arch, const WeightMap& weights,
                                           const EngineOptions& options, int B, bool native, int num_cus,
                                           std::vector<Op>* engine_ops = nullptr, int num_classes = 1000,
-                                          int image_size = 224, int topk = 1, bool tensor_in = false);
+                                          int image_size = 224, int topk = 1, bool tensor_in = false,
+                                          bool features = false);
   std::vector<PlanLine> plan_lines(const std::vector<Step>& steps) const;
   void* weight_arena() const { return warena_; }
 
@@ -260,6 +272,7 @@ class Engine {
   int image_size() const { return image_size_; }
   int max_batch() const { return max_batch_; }
   int num_cus() const { return num_cus_; }
+  int feature_dim() const;  // length of the vector the classifier's last fc reads (512 / 2048 / 4096)
   const EngineOptions& options() const { return opt_; }
   hipStream_t stream() const { return stream_; }  // the engine's own (capture) stream
   size_t weight_bytes() const { return weight_bytes_; }
@@ -280,8 +293,14 @@ class Engine {
   // prob f32 [B, k] in descending order (softmax_topk's contract), 1 <= k <=
   // min(num_classes, kMaxTopK). k = 1 is forward(); for k > 1 the tail's own
   // top-1 goes to engine scratch and one more kernel ranks the logits.
+  // features: device fp32 [B, feature_dim()], or null. The vector the last fc
+  // reads (the pooled feature; AlexNet's classifier.4 output), widened from
+  // the bf16 the fc multiplies; l2norm: each row scaled to unit L2 norm
+  // (embed_rows). One more launch after the forward's own, which are
+  // unchanged. Graphs are keyed by the pointer and the flag as well.
   void forward_topk(const uint8_t* images, int B, int Hin, int Win, int k, int32_t* idx, float* prob,
-                    float* logits, hipStream_t stream, bool use_graph);
+                    float* logits, hipStream_t stream, bool use_graph, float* features = nullptr,
+                    bool l2norm = false);
   // The same forward on a float tensor the caller has already normalised:
   // x is device [B, 3, S, S] contiguous, or [B, S, S, 3] contiguous with
   // channels_last, S = image_size(), of dtype dt (pack_tensor's contract: the
@@ -289,7 +308,8 @@ class Engine {
   // forward_topk()'s. Graphs are keyed by the input kind as well, so a u8 and
   // a tensor forward, or two dtypes, on one pointer never replay each other's.
   void forward_tensor(const void* x, TensorDType dt, bool channels_last, int B, int k, int32_t* idx, float* prob,
-                      float* logits, hipStream_t stream, bool use_graph);
+                      float* logits, hipStream_t stream, bool use_graph, float* features = nullptr,
+                      bool l2norm = false);
 
   // Eager forward with an event pair around every op: (op name, ms).
   std::vector<std::pair<std::string, float>> profile(const uint8_t* images, int B, int Hin,
@@ -332,10 +352,12 @@ class Engine {
     bool channels_last = false;
     int kind() const { return tensor ? 1 + 2 * (int)dt + (channels_last ? 1 : 0) : 0; }  // graph key
   };
+  // A plan that ends with Embed writes features (normalised: l2norm).
   void run_ops(const std::vector<Step>& steps, const Input& in, int B, int32_t* idx, float* prob, float* logits,
-               hipStream_t s, std::vector<hipEvent_t>* evs, bool trace);
+               hipStream_t s, std::vector<hipEvent_t>* evs, bool trace, float* features = nullptr,
+               bool l2norm = false);
   void forward_input(const Input& in, int B, int k, int32_t* idx, float* prob, float* logits, hipStream_t stream,
-                     bool use_graph);
+                     bool use_graph, float* features, bool l2norm);
   // A conv op's launch arguments in two parts: the geometry (shapes, padding,
   // flags, scales, tile, split-K, persistent grid), which is all the planner
   // and the kernels' *_supported checks see, and the operands (x, w, bias,
@@ -380,7 +402,8 @@ class Engine {
   bool last_stream_valid_ = false;
   hipStream_t side_ = nullptr;                      // downsample branch
   std::vector<hipEvent_t> fork_evs_, join_evs_;     // per op
-  using GraphKey = std::tuple<const void*, int, int, int, void*, void*, void*, int, int>;  // ..., logits, k, Input::kind
+  // ..., logits, k, Input::kind, features, l2norm
+  using GraphKey = std::tuple<const void*, int, int, int, void*, void*, void*, int, int, void*, int>;
   std::map<GraphKey, hipGraphExec_t> graphs_;
 };
 

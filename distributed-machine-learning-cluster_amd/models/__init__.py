@@ -3,6 +3,7 @@
 The GPU engine (``dmlc.runtime.InferenceEngine``) builds the same graphs in
 C++ (csrc/runtime/engine.cpp) from the same parameter names.
 """
-from .reference import ARCHS, AlexNet, BasicBlock, Bottleneck, ResNet, build, state_dict_f32  # noqa: F401
+from .reference import (ARCHS, AlexNet, BasicBlock, Bottleneck, ResNet, build, penultimate_features,  # noqa: F401
+                        state_dict_f32)
 
 SUPPORTED = tuple(sorted(ARCHS))

@@ -155,3 +155,19 @@ def state_dict_f32(model: nn.Module) -> dict[str, torch.Tensor]:
     """Float32 parameters + BN running stats (drops num_batches_tracked)."""
     return {k: v.detach().float().contiguous() for k, v in model.state_dict().items()
             if not k.endswith("num_batches_tracked")}
+
+
+@torch.no_grad()
+def penultimate_features(model: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """The input of ``model``'s last ``nn.Linear`` on the batch ``x``
+    [B,3,H,W], for every zoo arch: the pooled 512 / 2048 features of a ResNet,
+    AlexNet's ``classifier.4`` output after its ReLU. The fp32 counterpart of
+    ``InferenceEngine.embed``."""
+    last = [m for m in model.modules() if isinstance(m, nn.Linear)][-1]
+    seen = []
+    h = last.register_forward_pre_hook(lambda mod, inp: seen.append(inp[0].detach().clone()))
+    try:
+        model(x)
+    finally:
+        h.remove()
+    return seen[0]

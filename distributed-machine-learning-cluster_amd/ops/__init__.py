@@ -915,6 +915,39 @@ def softmax_topk(logits: torch.Tensor, k: int, n: int | None = None) -> tuple[to
     return idx, prob
 
 
+def embed_rows(x: torch.Tensor, normalize: bool = False, scale: float | None = None,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """The feature rows of bf16 ``x`` [B,C], or the global average of bf16 /
+    e4m3 (uint8 or float8_e4m3fn, value = e4m3 * ``scale``) ``x`` [B,HW,C]
+    exactly as ``avgpool_global`` rounds it to bf16, as fp32 [B,C];
+    ``normalize``: every row divided by max(its L2 norm, 1e-12), like
+    ``F.normalize`` (csrc/kernels/embed.hip). C % 8 == 0, C <= 8192. ``out``:
+    a contiguous fp32 [B,C] tensor on x's device to write instead of a new one."""
+    _need_cuda(x)
+    fp8 = x.dtype in (torch.uint8, FP8)
+    if not fp8 and x.dtype != torch.bfloat16:
+        raise ValueError(f"embed_rows expects bf16 or e4m3 (uint8) rows, got {x.dtype}")
+    if x.dim() not in (2, 3) or (fp8 and x.dim() != 3):
+        raise ValueError(f"embed_rows expects bf16 [B,C] / [B,HW,C] or e4m3 [B,HW,C], got {tuple(x.shape)}")
+    if fp8 and scale is None:
+        raise ValueError("embed_rows: an e4m3 input needs its scale")
+    if not fp8 and scale is not None:
+        raise ValueError("embed_rows: scale goes with an e4m3 input")
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.shape[1] if x.dim() == 3 else 1
+    nat = native()
+    if not nat.embed_rows_supported(HW, C) or (fp8 and HW == 1):
+        raise ValueError(f"embed_rows: needs HW >= 1 (> 1 for e4m3), C % 8 == 0 and C <= 8192, got HW={HW} C={C}")
+    x = x.contiguous()
+    if out is None:
+        out = torch.empty(B, C, device=x.device, dtype=torch.float32)
+    elif (out.device != x.device or out.dtype != torch.float32 or tuple(out.shape) != (B, C)
+          or not out.is_contiguous()):
+        raise ValueError(f"embed_rows: out must be contiguous float32 [{B},{C}] on {x.device}")
+    nat.embed_rows(_ptr(x), _ptr(out), B, HW, C, fp8, float(scale) if fp8 else 1.0, bool(normalize), _stream())
+    return out
+
+
 # ---------------------------------------------------------------- split JPEG decode
 def _align(n: int, a: int = 256) -> int:
     return (n + a - 1) // a * a

@@ -45,6 +45,9 @@ class InferenceEngine:
         self.num_classes = num_classes
         self.image_size = image_size
         self.max_topk = min(num_classes, C.MAX_TOPK)  # largest predict(topk=)
+        # length of the vector the last fc reads: 512 (ResNet18/34), 2048 (ResNet50), 4096 (AlexNet)
+        self.feature_dim = self._e.feature_dim
+        self._scratch = None  # embed(): idx / prob nobody reads
 
     @property
     def gflop_per_image(self) -> float:
@@ -55,7 +58,7 @@ class InferenceEngine:
         return self._e.weight_bytes
 
     def predict(self, images: torch.Tensor, use_graph: bool = True, out=None, return_logits: bool = False,
-                topk: int = 1):
+                topk: int = 1, return_features: bool = False, normalize_features: bool = False):
         """images: uint8 [B,H,W,3] on this engine's GPU. Returns (idx int32 [B],
         prob f32 [B]) (+ logits f32 [B,num_classes] if return_logits). topk > 1:
         idx and prob are [B,topk], the best classes in descending order (equal
@@ -66,25 +69,54 @@ class InferenceEngine:
         [B,3,image_size,image_size], contiguous or ``torch.channels_last``: the
         tensor a torch model takes. It is used as given (rounded to bf16): the
         caller resizes and normalises, with whatever mean/std the weights were
-        trained with. topk, out, return_logits and use_graph work the same."""
+        trained with. topk, out, return_logits and use_graph work the same.
+
+        return_features: ``features`` f32 [B,feature_dim] is appended to the
+        returned tuple (after logits): the vector the last fc reads, i.e. the
+        pooled feature of a ResNet or AlexNet's ``classifier.4`` output, widened
+        from the bf16 the fc multiplies; normalize_features: each row scaled to
+        unit L2 norm (``F.normalize``). One more kernel after the forward's
+        own; idx, prob and logits are the same bits with and without it."""
+        if normalize_features and not return_features:
+            raise ValueError("normalize_features needs return_features")
+        feats = (None, bool(normalize_features)) if return_features else None
+        return self._predict(images, use_graph, out, return_logits, topk, feats)
+
+    def embed(self, images: torch.Tensor, normalize: bool = False, use_graph: bool = True,
+              out: torch.Tensor | None = None) -> torch.Tensor:
+        """The ``features`` of ``predict(images, return_features=True,
+        normalize_features=normalize)`` alone: f32 [B,feature_dim]. images as
+        for ``predict``. ``out``: a contiguous float32 [B,feature_dim] tensor
+        on this engine's GPU to write instead of a new one. The forward's class
+        answer goes to a scratch pair."""
+        B = images.shape[0]
+        if out is not None and (out.device != self.device or out.dtype != torch.float32
+                                or tuple(out.shape) != (B, self.feature_dim) or not out.is_contiguous()):
+            raise ValueError(f"out: expected contiguous torch.float32 [{B},{self.feature_dim}] on {self.device}, got "
+                             f"{out.dtype} {tuple(out.shape)} on {out.device}")
+        if self._scratch is None:
+            self._scratch = (torch.empty(self.max_batch, dtype=torch.int32, device=self.device),
+                             torch.empty(self.max_batch, dtype=torch.float32, device=self.device))
+        answer = (self._scratch[0][:B], self._scratch[1][:B])
+        return self._predict(images, use_graph, answer, False, 1, (out, bool(normalize)))[-1]
+
+    def _predict(self, images, use_graph, out, return_logits, topk, feats):
+        """feats: None, or (features buffer or None for a new one, normalise)."""
         if images.is_floating_point():
-            return self._predict_tensor(images, use_graph, out, return_logits, topk)
+            if images.device != self.device:
+                raise ValueError(f"expected a float tensor on {self.device}, got one on {images.device}")
+            dt, channels_last = ops.tensor_input(images, self.image_size)
+            return self._forward(("tensor", images.data_ptr(), dt, channels_last), images.shape[0], use_graph, out,
+                                 return_logits, topk, feats)
         if images.device != self.device or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
             raise ValueError(f"expected uint8 [B,H,W,3] on {self.device}, got {images.dtype} {tuple(images.shape)} "
                              f"on {images.device}")
         if not images.is_contiguous():
             raise ValueError("images must be contiguous")
         B, H, W, _ = images.shape
-        return self._forward(("u8", images.data_ptr(), H, W), B, use_graph, out, return_logits, topk)
+        return self._forward(("u8", images.data_ptr(), H, W), B, use_graph, out, return_logits, topk, feats)
 
-    def _predict_tensor(self, x: torch.Tensor, use_graph, out, return_logits, topk):
-        if x.device != self.device:
-            raise ValueError(f"expected a float tensor on {self.device}, got one on {x.device}")
-        dt, channels_last = ops.tensor_input(x, self.image_size)
-        return self._forward(("tensor", x.data_ptr(), dt, channels_last), x.shape[0], use_graph, out, return_logits,
-                             topk)
-
-    def _forward(self, src, B, use_graph, out, return_logits, topk):
+    def _forward(self, src, B, use_graph, out, return_logits, topk, feats=None):
         if not isinstance(topk, int) or not 1 <= topk <= self.max_topk:
             raise ValueError(f"topk = {topk} outside 1..{self.max_topk}")
         if out is None:
@@ -100,19 +132,26 @@ class InferenceEngine:
                         raise ValueError(f"out: expected contiguous {dt} [{B},{topk}] on {self.device}, got "
                                          f"{t.dtype} {tuple(t.shape)} on {t.device}")
         logits = torch.empty(B, self.num_classes, dtype=torch.float32, device=self.device) if return_logits else None
+        features, l2norm = None, False
+        if feats is not None:
+            features, l2norm = feats
+            if features is None:
+                features = torch.empty(B, self.feature_dim, dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         lp = 0 if logits is None else logits.data_ptr()
+        fp = 0 if features is None else features.data_ptr()
         if src[0] == "tensor":
             _, ptr, dt, channels_last = src
             self._e.forward_tensor(ptr, dt, channels_last, B, topk, idx.data_ptr(), prob.data_ptr(), lp, stream,
-                                   use_graph)
-        elif topk == 1:
+                                   use_graph, features=fp, l2norm=l2norm)
+        elif topk == 1 and features is None:
             _, ptr, H, W = src
             self._e.forward(ptr, B, H, W, idx.data_ptr(), prob.data_ptr(), lp, stream, use_graph)
         else:
             _, ptr, H, W = src
-            self._e.forward_topk(ptr, B, H, W, topk, idx.data_ptr(), prob.data_ptr(), lp, stream, use_graph)
-        return (idx, prob, logits) if return_logits else (idx, prob)
+            self._e.forward_topk(ptr, B, H, W, topk, idx.data_ptr(), prob.data_ptr(), lp, stream, use_graph,
+                                 features=fp, l2norm=l2norm)
+        return tuple(t for t in (idx, prob, logits, features) if t is not None)
 
     def profile(self, images: torch.Tensor) -> list[tuple[str, float]]:
         """Per-op GPU time (ms) of one eager forward (hipEvent pairs)."""
