@@ -62,11 +62,6 @@ struct AlexStemArgs {
   bf16* y;             // [B, 27, 27, 64]
 };
 
-__device__ __forceinline__ int perm32(int n) {
-  const int nf = n >> 4, r = n & 15;
-  return 8 * (r >> 2) + 4 * nf + (r & 3);
-}
-
 // conv-ring byte offset of 16-B channel chunk c of pixel px
 __device__ __forceinline__ int conv_off(int px, int c) { return px * 128 + ((c ^ (px & 7)) << 4); }
 
@@ -150,25 +145,25 @@ __global__ __launch_bounds__(512, 1) void alex_stem_kernel(AlexStemArgs a) {
     col_of[ks] = (2 * ow + cc) * 16;
   }
 
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  lgkm_wait();
   __syncthreads();
   // prologue: raw rows of padded rows 0..22 (conv rows 0..3) by DMA into the
   // raw ring, converted here; then the raw rows of conv rows 4, 5 (padded
   // 23..30) and 6, 7 (31..38), one row per wave, converted at iterations 0
   // and 1 (31..38 reuse the slots of rows 0..6, converted by then)
   for (int pr = wave; pr < 23; pr += 8) dma_row(pr);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   __syncthreads();
   for (int it = tid; it < 23 * kChunks; it += 512) {
     const int pr = it / kChunks, p = it - pr * kChunks;
     convert_chunk(pr, p);
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  lgkm_wait();
   __syncthreads();
   dma_row(23 + wave);
   dma_row(31 + wave);
-  asm volatile("s_waitcnt vmcnt(1)" ::: "memory");  // conv rows 4, 5; 6, 7 may stay in flight
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  vm_wait<1>();  // conv rows 4, 5; 6, 7 may stay in flight
+  lgkm_wait();
   __syncthreads();
 
   // iteration i: conv rows r0 = 2i, r0 + 1; pooled row i - 2
@@ -235,11 +230,9 @@ __global__ __launch_bounds__(512, 1) void alex_stem_kernel(AlexStemArgs a) {
     // the next iteration converts conv rows r0+6, r0+7 (DMA'd one iteration
     // ago, or in the prologue): in LDS before the barrier; this iteration's
     // DMA may stay in flight
-    if (dma_now)
-      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (dma_now) vm_wait<1>();
+    else vm_wait<0>();
+    lgkm_wait();
     __syncthreads();
   }
 }

@@ -48,8 +48,6 @@ namespace dmlc {
 
 namespace {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-
 struct BnArgs {
   const uint8_t* x;    // [B, 56, 56, 256] e4m3 (value = e4m3 * res_scale)
   const uint8_t* w1;   // [64][256] e4m3 (per-row scales folded into a1)
@@ -82,47 +80,6 @@ constexpr int kCst = 7 * kM * 4;         // a1, b1, b2 (64 floats each), b3 (256
 constexpr int kST = kMF * 2;             // y stores per memory wave per step
 constexpr size_t kLds = (size_t)kRing * kSlot + 2 * kT2 + kXB + kCst;  // 161024 B
 static_assert(kLds <= 160 * 1024, "LDS budget");
-
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
-
-// values already within +-448
-__device__ __forceinline__ uint32_t f32x4_to_fp8_sat(const float* f) {
-  int v = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], v, true);
-  return (uint32_t)v;
-}
-__device__ __forceinline__ uint32_t f32x4_to_fp8(const float* f) {
-  float c[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) c[i] = fminf(fmaxf(f[i], -448.f), 448.f);
-  int v = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], 0, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], v, true);
-  return (uint32_t)v;
-}
-
-__device__ __forceinline__ void fp8x4_to_f32(uint32_t u, float* f) {
-  e4m3x4_to_f32(u, f);
-}
-
-// 16-B global load the compiler does not track: its wait is the kernel's own
-// (counted vm_wait + pin), so no compiler wait lands behind a later DMA
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4 gload16(const void* p) {
-  u32x4 v;
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
-template <typename T>
-__device__ __forceinline__ void pin(T& v) {
-  asm volatile("" : "+v"(v));
-}
 
 __device__ __forceinline__ void load8(const float* p, float* v) {
   const float4 lo = *(const float4*)p, h4 = *(const float4*)(p + 4);
@@ -445,7 +402,7 @@ struct Memory {
 #pragma unroll
         for (int h = 0; h < 4; ++h) {  // channels c3 + 4h .. +3 = acc[h]
           float v[4], rf[4];
-          fp8x4_to_f32(rw[h], rf);
+          e4m3x4_to_f32(rw[h], rf);
 #pragma unroll
           for (int i = 0; i < 4; i += 2) {  // the residual as v_pk_fma_f32
             const f32x2 q = __builtin_elementwise_fma(f32x2{rf[i], rf[i + 1]}, f32x2{rsi, rsi},
@@ -453,7 +410,7 @@ struct Memory {
             v[i] = __builtin_amdgcn_fmed3f(q.x, 0.f, 448.f);
             v[i + 1] = __builtin_amdgcn_fmed3f(q.y, 0.f, 448.f);
           }
-          q[h] = f32x4_to_fp8_sat(v);
+          q[h] = e4m3x4_from_f32(v[0], v[1], v[2], v[3]);
         }
         // non-temporal y stores (L2 kept for the x re-reads)
         __builtin_nontemporal_store(u32x4{q[0], q[1], q[2], q[3]}, (u32x4*)(yim + pix(k, f) + c3));

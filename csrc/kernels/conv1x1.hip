@@ -42,67 +42,6 @@ namespace dmlc {
 
 namespace {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
-// LDS reads/writes of this wave done, then the workgroup barrier (no
-// compiler fence: it would add a vmcnt(0) and drain the DMA pipeline)
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
-
-// Make the compiler treat v as (re)defined here, after a preceding wait:
-// uses of an asm-loaded register cannot be hoisted above the wait.
-template <typename T>
-__device__ __forceinline__ void pin(T& v) {
-  asm volatile("" : "+v"(v));
-}
-
-
-__device__ __forceinline__ void fp8x4_to_f32(uint32_t u, float* f) {
-  e4m3x4_to_f32(u, f);
-}
-// values already within +-448
-__device__ __forceinline__ uint32_t f32x4_to_fp8_sat(const float* f) {
-  int v = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], v, true);
-  return (uint32_t)v;
-}
-__device__ __forceinline__ uint32_t f32x4_to_fp8(const float* f) {
-  float c[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) c[i] = fminf(fmaxf(f[i], -448.f), 448.f);
-  int v = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], 0, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], v, true);
-  return (uint32_t)v;
-}
-
-// Counted global loads the compiler does not track (no implicit vmcnt(0)
-// waits in front of their uses: the kernel waits for them itself).
-__device__ __forceinline__ u32x2 gload8(const void* p) {
-  u32x2 v;
-  asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
-__device__ __forceinline__ u32x4 gload16(const void* p) {
-  u32x4 v;
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
-__device__ __forceinline__ uint32_t gload4(const void* p) {
-  uint32_t v;
-  asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
-
 // Chunk swizzle of the staged input rows (16-B chunks, RB bytes per pixel):
 // every 16-lane group of the B-fragment reads hits 16 distinct bank groups
 // (tests/test_layouts_cpu.py::test_conv1x1_lds_conflict_free).
@@ -403,7 +342,7 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void conv1x1_kernel(C1Arg
         v[2 * e] = __builtin_amdgcn_fmed3f(r.x, relu_lo2, 448.f);
         v[2 * e + 1] = __builtin_amdgcn_fmed3f(r.y, relu_lo2, 448.f);
       }
-      *(uint32_t*)((uint8_t*)a.y2 + m * a.N2 + wave * 16 + 4 * g) = f32x4_to_fp8_sat(v);
+      *(uint32_t*)((uint8_t*)a.y2 + m * a.N2 + wave * 16 + 4 * g) = e4m3x4_from_f32(v[0], v[1], v[2], v[3]);
     }
   };
 
@@ -503,15 +442,15 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void conv1x1_kernel(C1Arg
           float rf[CPL];
           if constexpr (OUT8) {
             if constexpr (CPL == 16) {
-              fp8x4_to_f32(rv[pf][j].x, rf);
-              fp8x4_to_f32(rv[pf][j].y, rf + 4);
-              fp8x4_to_f32(rv[pf][j].z, rf + 8);
-              fp8x4_to_f32(rv[pf][j].w, rf + 12);
+              e4m3x4_to_f32(rv[pf][j].x, rf);
+              e4m3x4_to_f32(rv[pf][j].y, rf + 4);
+              e4m3x4_to_f32(rv[pf][j].z, rf + 8);
+              e4m3x4_to_f32(rv[pf][j].w, rf + 12);
             } else if constexpr (CPL == 8) {
-              fp8x4_to_f32(rv[pf][j].x, rf);
-              fp8x4_to_f32(rv[pf][j].y, rf + 4);
+              e4m3x4_to_f32(rv[pf][j].x, rf);
+              e4m3x4_to_f32(rv[pf][j].y, rf + 4);
             } else {
-              fp8x4_to_f32(rv[pf][j], rf);
+              e4m3x4_to_f32(rv[pf][j], rf);
             }
 #pragma unroll
             for (int e = 0; e < CPL; e += 2) {
@@ -540,15 +479,17 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void conv1x1_kernel(C1Arg
 #pragma unroll
           for (int e = 0; e < CPL; ++e) v[e] = __builtin_amdgcn_fmed3f(v[e], relu_lo, 448.f);
           if constexpr (CPL == 16) {
-            const uint4 q4 = make_uint4(f32x4_to_fp8_sat(v), f32x4_to_fp8_sat(v + 4), f32x4_to_fp8_sat(v + 8),
-                                        f32x4_to_fp8_sat(v + 12));
+            const uint4 q4 =
+                make_uint4(e4m3x4_from_f32(v[0], v[1], v[2], v[3]), e4m3x4_from_f32(v[4], v[5], v[6], v[7]),
+                           e4m3x4_from_f32(v[8], v[9], v[10], v[11]), e4m3x4_from_f32(v[12], v[13], v[14], v[15]));
             *(uint4*)yp = q4;
             if constexpr (CH) {  // and into the chained reduce's input block
               const int p = pf * 16 + fr, c = n >> 4;
               *(uint4*)(ybuf + p * NP2 + ((c ^ (p & 15)) << 4)) = q4;
             }
-          } else if constexpr (CPL == 8) *(uint2*)yp = make_uint2(f32x4_to_fp8_sat(v), f32x4_to_fp8_sat(v + 4));
-          else *(uint32_t*)yp = f32x4_to_fp8_sat(v);
+          } else if constexpr (CPL == 8)
+            *(uint2*)yp = make_uint2(e4m3x4_from_f32(v[0], v[1], v[2], v[3]), e4m3x4_from_f32(v[4], v[5], v[6], v[7]));
+          else *(uint32_t*)yp = e4m3x4_from_f32(v[0], v[1], v[2], v[3]);
         } else if constexpr (CPL == 8) {
           *(uint4*)yp = pack8_relu(v, a.relu);  // ReLU on the packed bf16
         } else {

@@ -27,10 +27,6 @@ namespace dmlc {
 
 namespace {
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
 struct D13Args {
   const bf16* x;      // [B, 13, 13, CI]
   const bf16* wf;     // [CO/32][KT][2][64][8] fragment order (stream_frag_index, K = 9 CI)
@@ -116,8 +112,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_13_kernel(D13Args a) {
   };
 
   vm_wait<0>();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  lds_barrier();
 
 #pragma nounroll
   for (int pass = 0; pass < NGW / GPP; ++pass) {
@@ -206,7 +201,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_13_kernel(D13Args a) {
             }
           }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lgkm_wait();
         // 6 x 6 pooled pixels x 4 GPP chunks of 8 channels; post-ReLU bf16 >= 0,
         // so the max is an unsigned 16-bit max
         typedef unsigned short ushort8 __attribute__((ext_vector_type(8)));

@@ -39,11 +39,6 @@ namespace dmlc {
 
 namespace {
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
 struct BlockArgs {
   const bf16* x;       // [B, 56, 56, 64]
   const bf16* wf1;     // conv1 weights, fragment order [2][KS][2][64][8] (stream_frag_index, K = 576)
@@ -147,8 +142,7 @@ __device__ __forceinline__ void block_role(const BlockArgs& a, char* xring, char
   const floatx4* bias = (const floatx4*)(biasl + (PROD ? 0 : kC) + wn * 32 + 8 * g);
 
   vm_wait<0>();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  lds_barrier();
 
   const char* src_ring = PROD ? xring : tring;
   // consumer: the residual (x rows base .. base + 3 of its step), read from
@@ -276,8 +270,7 @@ __device__ __forceinline__ void block_role(const BlockArgs& a, char* xring, char
     // (an idle role's weight ring needs nothing: it is periodic over K steps)
     // t rows written and the next step's x rows landed, for every wave
     if constexpr (PROD) vm_wait<0>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    lds_barrier();
   }
 }
 
@@ -295,8 +288,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_block_kernel(BlockArgs a) {
   // both convs' biases behind the rings: [2][64] floats
   float* biasl = (float*)(tring + kRing * kSlot);
   if (tid < 2 * kC) biasl[tid] = tid < kC ? a.bias1[tid] : a.bias2[tid - kC];
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  lds_barrier();
   if (wave < 4)
     block_role<true, PD, DMA_KS>(a, xring, tring, biasl, wave & 3, lane);
   else

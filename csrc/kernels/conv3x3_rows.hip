@@ -31,11 +31,6 @@ namespace dmlc {
 
 namespace {
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
 // weight-chunk swizzle for output channel n (only bit 3 of n matters; the
 // wave's channel offsets are multiples of 16)
 __device__ __forceinline__ int wswz(int n) { return ((n >> 3) & 1) << 1; }

@@ -39,11 +39,6 @@ namespace dmlc {
 
 namespace {
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
 struct R28Args {
   const bf16* x;      // [B, 28, 28, 128]
   const bf16* wf;     // weights, fragment order [4][36][2][64][8] (stream_frag_index, K = 1152)
@@ -62,13 +57,6 @@ struct R28Args {
   const float* bds;
   int stagger;  // start_stagger (common.h)
 };
-
-// 4 floats (within +-448) -> 4 e4m3 bytes
-__device__ __forceinline__ uint32_t r28_e4m3x4(float a, float b, float c, float d) {
-  int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
-  return (uint32_t)v;
-}
 
 constexpr int kH = 28, kW = 28, kC = 128;
 constexpr int kR = 4;                 // output rows per step
@@ -114,8 +102,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_rows28_kernel(R28Args a) {
   const bf16* img = a.x + (long)b * kH * kW * kC;
 
   for (int o = tid * 16; o < kSlotsAlloc * kRB; o += NT * 16) *(uint4*)(ring + o) = make_uint4(0, 0, 0, 0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  lds_barrier();
   // input row yy -> ring slot (yy + 1) % kRing (+ guard slot kRing / kRing+1
   // for slots 0 / 1); wave w stages quarter plane w & 3: chunks 0..63 and
   // 64..111 of its run. Row 28 (below the image) reuses a slot: its run is
@@ -227,8 +214,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_rows28_kernel(R28Args a) {
   // first step's MFMAs wait for each K step's own fragments (the compiler's
   // counted waits), so the load overlaps the first step instead of preceding it
   vm_wait<63>();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  lds_barrier();
 
   // step 0 is peeled (a separate copy of the body): at a loop header the
   // compiler waits for every outstanding load (vmcnt(0)), which would put the
@@ -351,7 +337,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_rows28_kernel(R28Args a) {
             for (int e = 0; e < 8; ++e)
               q[e] = fminf(fmaxf((a.relu ? fmaxf(v[e], 0.f) : v[e]) * a.out_inv_scale, -448.f), 448.f);
             *(uint2*)((uint8_t*)a.y + obase + (long)(16 * ff + fr) * kC) =
-                make_uint2(r28_e4m3x4(q[0], q[1], q[2], q[3]), r28_e4m3x4(q[4], q[5], q[6], q[7]));
+                make_uint2(e4m3x4_from_f32(q[0], q[1], q[2], q[3]), e4m3x4_from_f32(q[4], q[5], q[6], q[7]));
           } else {
             *(uint4*)(a.y + obase + (long)(16 * ff + fr) * kC) = pack8_relu(v, a.relu);
           }
@@ -363,8 +349,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_rows28_kernel(R28Args a) {
     // step's kMF stores (step 0: its K loop already drained every load, the
     // compiler's waits on the weights)
     vm_wait<kMF>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    lds_barrier();
   };
   step_body(0);
   for (int step = 1; step < kSteps; ++step) step_body(step);

@@ -35,11 +35,6 @@ namespace dmlc {
 
 namespace {
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
 struct S2Args {
   const bf16* x;      // [B, 56, 56, 64]
   const bf16* wf;     // 3x3 weights, fragment order [4][18][2][64][8] (stream_frag_index, K = 576)
@@ -89,8 +84,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_s2rows_kernel(S2Args a) {
   // shared zero page read by every workgroup's pad lanes is one hot L2
   // channel per XCD).
   for (int o = tid * 16; o < kSlotsAlloc * kRB; o += 256 * 16) *(uint4*)(ring + o) = make_uint4(0, 0, 0, 0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  lds_barrier();
   // input row yy >= 0 -> ring slot (yy + 1) % 17, and guard slot 17 / 18 too
   // for slots 0 / 1: per K-half plane the 224 chunks of slots 1..56 are one
   // contiguous run; wave w DMAs chunks 64 w .. 64 w + 63 of both runs
@@ -224,8 +218,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_s2rows_kernel(S2Args a) {
     // still be in flight: vmcnt retires in order) and every wave is done
     // reading the rows they replace
     vm_wait<(DS ? 2 : 1) * kMF>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    lds_barrier();
   };
   step_body(0);
   for (int step = 1; step < kSteps; ++step) step_body(step);

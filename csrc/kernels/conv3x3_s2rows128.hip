@@ -37,11 +37,6 @@ namespace dmlc {
 
 namespace {
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
 struct S2R128Args {
   const bf16* x;    // [B, 56, 56, 128]
   const bf16* wf;   // weights, fragment order [4][36][2][64][8] (stream_frag_index, K = 1152)
@@ -68,13 +63,6 @@ static_assert((size_t)kSlotsAlloc * kRB <= 160 * 1024, "LDS budget");
 
 __device__ __forceinline__ int swz_of(int y, int x) { return ((((y + 1) >> 1) * kW + ((x + 1) >> 1)) >> 1) & 3; }
 
-// 4 floats (within +-448) -> 4 e4m3 bytes
-__device__ __forceinline__ uint32_t s2r_e4m3x4(float a, float b, float c, float d) {
-  int v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
-  return (uint32_t)v;
-}
-
 template <bool OUT8>
 __global__ __launch_bounds__(256, 1) void conv3x3_s2rows128_kernel(S2R128Args a) {
   extern __shared__ __attribute__((aligned(16))) uint4 smem[];
@@ -87,8 +75,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_s2rows128_kernel(S2R128Args a)
 
   // pad slots, the spare guard copies and the zero row y = -1 (slot 0): zero once
   for (int o = tid * 16; o < kSlotsAlloc * kRB; o += 256 * 16) *(uint4*)(ring + o) = make_uint4(0, 0, 0, 0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  lds_barrier();
   // input row yy >= 0 -> ring slot (yy + 1) % 9 (and guard slot 9 / 10 for
   // slots 0 / 1): per quarter plane the 224 chunks of slots 1..56 are one
   // contiguous run; wave w DMAs chunks 64 w .. 64 w + 63 of all four runs
@@ -202,7 +189,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_s2rows128_kernel(S2R128Args a)
 #pragma unroll
         for (int e = 0; e < 8; ++e)
           qv[e] = fminf(fmaxf((a.relu ? fmaxf(v[e], 0.f) : v[e]) * a.out_inv_scale, -448.f), 448.f);
-        const uint2 pk = make_uint2(s2r_e4m3x4(qv[0], qv[1], qv[2], qv[3]), s2r_e4m3x4(qv[4], qv[5], qv[6], qv[7]));
+        const uint2 pk =
+            make_uint2(e4m3x4_from_f32(qv[0], qv[1], qv[2], qv[3]), e4m3x4_from_f32(qv[4], qv[5], qv[6], qv[7]));
         if (p < kNPix) *(uint2*)((uint8_t*)a.y + o) = pk;
       } else {
         const uint4 pk = pack8_relu(v, a.relu);
@@ -213,8 +201,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_s2rows128_kernel(S2R128Args a)
     // in flight: vmcnt retires in order) and every wave is done reading the
     // rows they replace
     vm_wait<kMF>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    lds_barrier();
   };
   step_body(0);
   for (int step = 1; step < kSteps; ++step) step_body(step);

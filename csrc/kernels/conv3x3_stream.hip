@@ -47,12 +47,6 @@ namespace dmlc {
 
 namespace {
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
 struct StreamConvArgs {
   const bf16* x;      // [B, S*H, S*W, CI]
   const bf16* w;      // [CO, 9*CI], k = (kh*3 + kw)*CI + c
@@ -87,21 +81,6 @@ struct StreamConvArgs {
 struct alignas(8) u32x2s {
   uint32_t x, y;
 };
-// 4 floats (>= -448, <= 448) -> 4 e4m3 bytes
-__device__ __forceinline__ uint32_t e4m3x4(float a, float b, float c, float d) {
-  int v = __builtin_amdgcn_cvt_pk_fp8_f32(fmaxf(a, -448.f), fmaxf(b, -448.f), 0, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(fmaxf(c, -448.f), fmaxf(d, -448.f), v, true);
-  return (uint32_t)v;
-}
-
-// Weight-row permutation inside a wave's 32-row tile: row n = 16nf + r holds
-// channel 8(r>>2) + 4nf + (r&3) of the group, so the lane with accumulator
-// rows 4fq..4fq+3 of fragments 0 and 1 owns the 8 consecutive channels
-// 8fq .. 8fq+7.
-__device__ __forceinline__ int perm32(int n) {
-  const int nf = n >> 4, r = n & 15;
-  return 8 * (r >> 2) + 4 * nf + (r & 3);
-}
 
 // Weight-tile chunk swizzle (physical 16-B chunk of logical chunk c of a 64-B
 // row n), as conv_bigtile.hip: conflict-free for the fragment reads (lane
@@ -517,8 +496,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_stream_kernel(StreamConvArgs a
 #pragma unroll
         for (int e = 0; e < 8; ++e) q[e] = fminf((relu ? fmaxf(v[e], 0.f) : v[e]) * a.out_inv_scale, 448.f);
         u32x2s o;
-        o.x = e4m3x4(q[0], q[1], q[2], q[3]);
-        o.y = e4m3x4(q[4], q[5], q[6], q[7]);
+        o.x = e4m3x4_from_f32_clamped_below(q[0], q[1], q[2], q[3]);
+        o.y = e4m3x4_from_f32_clamped_below(q[4], q[5], q[6], q[7]);
         *(u32x2s*)((uint8_t*)a.y + off) = o;
       } else if (a.store_y) {
         *(uint4*)(a.y + off) = packed;
@@ -584,7 +563,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_stream_kernel(StreamConvArgs a
     }
   }
   if (a.stamps && tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
     unsigned long long* sp = a.stamps + blockIdx.x * 4;
     sp[0] = t_start;
     sp[1] = t_first;

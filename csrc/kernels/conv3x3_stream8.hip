@@ -41,8 +41,6 @@ namespace dmlc {
 
 namespace {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-
 struct Stream8Args {
   const uint8_t* x;     // [B, H, W, CI] e4m3
   const uint8_t* wf;    // e4m3 weights in stream8 fragment order (conv3x3_stream8_frag_offset)
@@ -212,8 +210,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_stream8_kernel(Stream8Args a) 
   };
 
   set_tap(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own input DMAs (and the first weights)
-  __builtin_amdgcn_s_barrier();                     // everyone's
+  vm_wait<0>();                  // own input DMAs (and the first weights)
+  __builtin_amdgcn_s_barrier();  // everyone's
   asm volatile("" ::: "memory");
   v8i xf[MF];
 #pragma unroll
@@ -290,11 +288,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_stream8_kernel(Stream8Args a) 
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) q[e] = __builtin_amdgcn_fmed3f(q[e], lo_clamp, 448.f);
-      int lo = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], lo, true);
-      int hi = __builtin_amdgcn_cvt_pk_fp8_f32(q[4], q[5], 0, false);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(q[6], q[7], hi, true);
-      *(uint2*)(a.y + base + 32 * j + (long)p * CO) = make_uint2((uint32_t)lo, (uint32_t)hi);
+      *(uint2*)(a.y + base + 32 * j + (long)p * CO) =
+          make_uint2(e4m3x4_from_f32(q[0], q[1], q[2], q[3]), e4m3x4_from_f32(q[4], q[5], q[6], q[7]));
     }
   }
 }

@@ -28,11 +28,6 @@ namespace dmlc {
 
 namespace {
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
 struct D27Args {
   const bf16* x;      // [B, 27, 27, 64]
   const bf16* wf;     // [6][50][2][64][8] fragment order (stream_frag_index, K = 1600)
@@ -116,8 +111,7 @@ __global__ __launch_bounds__(512, 1) void conv5x5_27_kernel(D27Args a) {
   };
 
   vm_wait<0>();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  lds_barrier();
 
 #pragma nounroll
   for (int pass = 0; pass < kCO / 32 / kGPP; ++pass) {

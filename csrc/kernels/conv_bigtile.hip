@@ -47,7 +47,6 @@ namespace {
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // 64-B LDS rows (4 chunks of 16 B): physical chunk = chunk ^ (3 * bit 2 of
 // the row). With the ds_read_b128 lane groups {0-3,12-15,20-27},
@@ -55,23 +54,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // reads chunk lane>>4 of row base+(lane&15), base % 16 == 0) puts each group
 // on 16 distinct 16-B bank slots: conflict-free.
 __device__ __forceinline__ int bt_swz(int row, int chunk) { return chunk ^ (3 * ((row >> 2) & 1)); }
-
-// s_waitcnt vmcnt(N) with a compile-time N.
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
-// Buffer descriptor from provably wave-uniform inputs (else hipcc wraps every
-// buffer op in a waterfall loop: cdna_hip_programming.md T20).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bt_rsrc(const float* p, int bytes) {
-  const uint64_t u = (uint64_t)p;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0,
-                                           __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
 
 constexpr unsigned kSpinLimit = 1u << 21;  // x (poll + s_sleep) ~ 1-2 s: a hang becomes an error
 constexpr int kMaxFlags = 4096;
@@ -269,8 +251,7 @@ __global__ __launch_bounds__(512, 1) void conv_bt_kernel(ConvArgs a, int k_tiles
   int st = 0;
   for (int t = k0; t < k1; ++t) {
     vm_wait<(D - 1) * G>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    lds_barrier();
     asm volatile("" ::: "memory");
     const int tn = t + D;
     const bool valid = tn < k1;
@@ -333,8 +314,8 @@ __global__ __launch_bounds__(512, 1) void conv_bt_kernel(ConvArgs a, int k_tiles
   const int cq = wn * WTN + q * 8;  // tile column of this lane's 8 channels
   const int nq = n0 + cq;
   const __amdgpu_buffer_rsrc_t slab_rs =
-      bt_rsrc(slabs + (size_t)(tile * nslot + (slice > 0 ? slice - 1 : 0)) * kSlabFloats,
-              splits > 1 ? (slice > 0 ? BM * BN * 4 : nslot * kSlabFloats * 4) : 0);
+      wave_rsrc(slabs + (size_t)(tile * nslot + (slice > 0 ? slice - 1 : 0)) * kSlabFloats,
+                splits > 1 ? (slice > 0 ? BM * BN * 4 : nslot * kSlabFloats * 4) : 0);
   floatx4 bq0 = {0.f, 0.f, 0.f, 0.f}, bq1 = bq0;
   if (slice == 0 && a.bias && nq < a.N) {
     bq0 = *(const floatx4*)(a.bias + nq);
@@ -351,7 +332,7 @@ __global__ __launch_bounds__(512, 1) void conv_bt_kernel(ConvArgs a, int k_tiles
         *(floatx4*)(wl + row * 64 + chunk * 4) = acc[i][h * 4 + jj];
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm_wait();
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
       const int row = g * 8 + rr;
@@ -383,10 +364,10 @@ __global__ __launch_bounds__(512, 1) void conv_bt_kernel(ConvArgs a, int k_tiles
       const uint4 pv = pack8_relu(v, a.relu);
       *(uint4*)((bf16*)a.y + o) = pv;
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads done before the next half overwrites
+    lgkm_wait();  // reads done before the next half overwrites
   }
   if (slice > 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains before the signal
+    vm_wait<0>();  // every storing wave drains before the signal
     __syncthreads();
     if (tid == 0) __hip_atomic_store(flags + tile * nslot + slice - 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -541,8 +522,7 @@ __global__ __launch_bounds__(512, 1) void conv_btp_kernel(ConvArgs a, int k_tile
     for (int kk = 0; kk < k_tiles; ++kk) {
       const int i = base + kk;
       wait_younger<D, G>(items - 1 - i);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
+      lds_barrier();
       asm volatile("" ::: "memory");
       if (i + D < items) issue(i + D, st == 0 ? NS - 1 : st - 1);
       compute(st);
@@ -552,8 +532,7 @@ __global__ __launch_bounds__(512, 1) void conv_btp_kernel(ConvArgs a, int k_tile
     // after this barrier no wave reads it, and it is refilled only after the
     // next K-loop barrier, which every wave reaches after its epilogue reads.
     const int est = st == 0 ? NS - 1 : st - 1;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    lds_barrier();
     asm volatile("" ::: "memory");
     float* wl = (float*)((char*)smem + est * STAGE_B) + wave * (16 * 64);
     const int m0 = (tile / n_tiles) * BM, n0 = (tile % n_tiles) * BN;
@@ -567,7 +546,7 @@ __global__ __launch_bounds__(512, 1) void conv_btp_kernel(ConvArgs a, int k_tile
     for (int j = 0; j < TM; ++j) {  // pass j: rows j*16 .. j*16+15 of the wave tile
 #pragma unroll
       for (int i = 0; i < TN; ++i) *(floatx4*)(wl + fr * 64 + (((i * 4 + fq) ^ fr) * 4)) = acc[i][j];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      lgkm_wait();
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
         const int row = g * 8 + rr;
@@ -586,7 +565,7 @@ __global__ __launch_bounds__(512, 1) void conv_btp_kernel(ConvArgs a, int k_tile
         }
         *(uint4*)((bf16*)a.y + o) = pack8_relu(v, a.relu);
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads done before the next pass overwrites
+      lgkm_wait();  // reads done before the next pass overwrites
     }
   }
 }

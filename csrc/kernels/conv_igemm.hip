@@ -58,22 +58,8 @@ __device__ __forceinline__ int swzk(int row, int chunk) {
   return IN8 ? chunk ^ ((row >> 1) & 5) : swz(row, chunk);
 }
 
-typedef int v8i __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ v8i cat8(uint4 lo, uint4 hi) {
   return v8i{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
-}
-
-// e4m3 helpers (OCP, gfx950): 4 bytes <-> 4 floats; stores saturate at +-448.
-__device__ __forceinline__ void fp8x4_to_f32(uint32_t u, float* f) {
-  e4m3x4_to_f32(u, f);
-}
-__device__ __forceinline__ uint32_t f32x4_to_fp8(const float* f) {
-  float c[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) c[i] = fminf(fmaxf(f[i], -448.f), 448.f);
-  int v = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], 0, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], v, true);
-  return (uint32_t)v;
 }
 
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
@@ -82,13 +68,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int q = nwg / 8, r = nwg % 8;
   const int xcd = bid % 8, local = bid / 8;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-}
-
-// s_waitcnt vmcnt(N) with a compile-time N (the field is an immediate).
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
 }
 
 // Leave at most min(D-1, remaining) tiles (G DMA instructions each) of this
@@ -342,7 +321,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a, int kt_p
         if (res) {
           if constexpr (OUT8) {  // the residual is the block's previous output: same dtype as y
             float rf[4];
-            fp8x4_to_f32(*(const uint32_t*)((const uint8_t*)a.res + o), rf);
+            e4m3x4_to_f32(*(const uint32_t*)((const uint8_t*)a.res + o), rf);
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] += rf[r] * a.res_scale;
           } else {
@@ -360,7 +339,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a, int kt_p
         if constexpr (OUT8) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] *= a.out_inv_scale;
-          *(uint32_t*)((uint8_t*)a.y + o) = f32x4_to_fp8(v);
+          *(uint32_t*)((uint8_t*)a.y + o) = e4m3x4_from_f32_clamped(v);
         } else if (a.out_f32) {
           *(floatx4*)((float*)a.y + o) = floatx4{v[0], v[1], v[2], v[3]};
         } else {
@@ -397,7 +376,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a, int kt_p
     for (int j = 0; j < TM; ++j) {
 #pragma unroll
       for (int i = 0; i < TN; ++i) *(floatx4*)(wl + fr * 64 + (((i * 4 + fq) ^ fr) * 4)) = acc[i][j];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      lgkm_wait();
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
         const int row = g * 8 + rr;
@@ -420,8 +399,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a, int kt_p
           float r[8];
           if constexpr (OUT8) {  // the residual is the block's previous output: same dtype as y
             const uint2 rv = *(const uint2*)((const uint8_t*)a.res + o);
-            fp8x4_to_f32(rv.x, r);
-            fp8x4_to_f32(rv.y, r + 4);
+            e4m3x4_to_f32(rv.x, r);
+            e4m3x4_to_f32(rv.y, r + 4);
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] += r[e] * a.res_scale;
           } else {
@@ -437,12 +416,12 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a, int kt_p
         if constexpr (OUT8) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] *= a.out_inv_scale;
-          *(uint2*)((uint8_t*)a.y + o) = make_uint2(f32x4_to_fp8(v), f32x4_to_fp8(v + 4));
+          *(uint2*)((uint8_t*)a.y + o) = make_uint2(e4m3x4_from_f32_clamped(v), e4m3x4_from_f32_clamped(v + 4));
         } else {
           *(uint4*)((bf16*)a.y + o) = pack8(v);
         }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads done before the next pass overwrites
+      lgkm_wait();  // reads done before the next pass overwrites
     }
   };
   // 16-B rows need N, ldo multiples of 8 and 16-B aligned y / residual
@@ -464,8 +443,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a, int kt_p
       int m0c = m0, n0c = n0;
       for (int it = 0; it < nk; ++it) {
         vm_wait<0>();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        lds_barrier();
         asm volatile("" ::: "memory");
         if (it + 1 < nk) {
           stage(kt0 + it + 1, st ^ 1);
@@ -483,8 +461,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a, int kt_p
       if (lds_epi) {
         // every wave has finished reading the stage it just computed (st ^ 1);
         // the next tile's first K-tile is landing in the other one
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        lds_barrier();
         asm volatile("" ::: "memory");
         epilogue_lds(m0c, n0c, st ^ 1);
       } else {
@@ -504,8 +481,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a, int kt_p
     int st = 0;
     for (int it = 0; it < nk; ++it) {
       wait_tiles<D, G>(min(D - 1, nk - 1 - it));
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
+      lds_barrier();
       asm volatile("" ::: "memory");
       if (it + D < nk) {
         const int ls = st == 0 ? NS - 1 : st - 1;  // stage of tile it-1 == stage of tile it+D

@@ -37,11 +37,6 @@ namespace dmlc {
 
 namespace {
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
 struct SmallArgs {
   const bf16* x;      // [B, H, W, CI]
   const bf16* wf;     // [CO/32][9 CI/32][2][64][8] fragment order
@@ -149,8 +144,7 @@ __global__ __launch_bounds__(256, 1) void conv_small_kernel(SmallArgs a) {
   // still be in flight: vmcnt retires in order) for every wave
   // (waves with fewer K steps issued fewer loads: wait for the smallest count)
   vm_wait<KT / 4 + (DS ? KPT / 4 : 0)>();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  lds_barrier();
 
   floatx4 acc[MF], accd[MF];
 #pragma unroll
@@ -189,8 +183,7 @@ __global__ __launch_bounds__(256, 1) void conv_small_kernel(SmallArgs a) {
     part[(wave * MF + f) * 64 + lane] = acc[f];
     if constexpr (DS) part[(4 * MF + wave * MF + f) * 64 + lane] = accd[f];
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  lds_barrier();
 
   const int ch = 32 * g + 8 * fq + 4 * nf;  // this lane's 4 output channels
   const floatx4 bs = *(const floatx4*)(a.bias + ch);

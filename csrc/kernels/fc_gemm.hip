@@ -37,11 +37,6 @@ constexpr int kBB = kBN * kKB * 2;  // 16 KB B stage
 constexpr int kStage = kAB + kBB;
 static_assert(kAB / 1024 == 32 && kBB / 1024 == 16, "6 DMA instructions per wave per stage");
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
 // 16-B chunk c (0..7) of a 128-B LDS row r
 __device__ __forceinline__ int fc_off(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
 
@@ -130,7 +125,7 @@ __global__ __launch_bounds__(512, 1) void fc_gemm_kernel(const bf16* __restrict_
         for (int nf = 0; nf < 2; ++nf)
           acc[mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mf], bf[nf], acc[mf][nf], 0, 0, 0);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (this wave's reads of the slot are done)
+    lgkm_wait();  // (this wave's reads of the slot are done)
   }
   // D lane (fr, fq): row 4 fq + r of the fragment, column fr
   float* wsp = ws + (long)ks * M * Npad;

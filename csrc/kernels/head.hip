@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void head_kernel(HeadArgs a) {
         const int i = k / cpr, jb = k - i * cpr;
         dma16(a.pooled + (long)(b0 + i) * C + jb * 512 + lane * 8, pooled + i * ldp + jb * 512);
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      vm_wait<0>();
     } else {
       for (int it = tid; it < nimg * c8; it += 256) {
         const int i = it / c8, cg = it - i * c8;
@@ -334,7 +334,7 @@ __global__ __launch_bounds__(256) void head_kernel(HeadArgs a) {
   // ---- 4. last arriver of group g combines the NS partials: lane li of an
   // image's TPI threads loads partial li (all loads of the workgroup in
   // flight together), then a butterfly merge (fixed order: deterministic)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   __syncthreads();
   int* flag = (int*)lg;  // reuse LDS (every wave is past its lg reads: barrier above)
   if (tid == 0) {

@@ -9,8 +9,6 @@ namespace dmlc {
 
 namespace {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-
 __global__ __launch_bounds__(64) void mfma_fp8_probe_kernel(const int* a, const int* b, float* d) {
   const int l = threadIdx.x;
   v8i A, B;

@@ -98,16 +98,6 @@ struct StemArgs {
 constexpr int kStemStampWgs = 16;
 constexpr int kStemStagger = 2;
 
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
-// LDS address of a pointer into __shared__ memory.
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
-
 // 16-bit LDS stores issued as inline asm: the compiler's waitcnt pass would
 // otherwise put an s_waitcnt vmcnt(0) in front of every LDS store (it cannot
 // tell them apart from the in-flight LDS-DMA of the input ring), stalling
@@ -118,11 +108,6 @@ __device__ __forceinline__ void ds_write_lo16(uint32_t addr, uint32_t v, const i
 }
 __device__ __forceinline__ void ds_write_hi16(uint32_t addr, uint32_t v, const int off) {
   asm volatile("ds_write_b16_d16_hi %0, %1 offset:%2" ::"v"(addr), "v"(v), "i"(off));
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
 }
 
 // y[l] = x[(l - 16) mod 64]: rotate the wave's four 16-lane rows down by one
@@ -366,8 +351,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_pool_kernel(
     for (int i = 0; i < a.stagger; ++i) __builtin_amdgcn_s_sleep(32);  // ~2048 cycles each
   if constexpr (U8) {  // the raw ring's pads stay zero (the DMA writes rows only)
     for (int o = tid * 16; o < RING * UBS; o += 256 * 16) *(uint4*)(u8ring + o) = make_uint4(0, 0, 0, 0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    lds_barrier();
   }
   // Prologue: rows for step 0 (the 13 rows of c0(0), negative ones skipped).
   load_rows(4 * ph0 - 8, 13);
@@ -703,14 +687,12 @@ __global__ __launch_bounds__(512, 1) void stem_roles_kernel(StemArgs a) {
   // 0 and at steps 0, 1), rows 0..4 converted by everyone (step 0 reads
   // paired rows -8..4)
   for (int o = tid * 16; o < kRolesRawRing * UBS; o += 512 * 16) *(uint4*)(u8ring + o) = make_uint4(0, 0, 0, 0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  lds_barrier();
   if (!mfma_wave) load_rows(0, 21);
   vm_wait<0>();
   __builtin_amdgcn_s_barrier();
   convert_rows(0, 5, tid, 512);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  lds_barrier();
 
   // stamps[(b * (T + 2) + t) * 4 + k]: k = 0 step start / 1 MFMA phase done
   // (wave 0), 2 helper work issued / 3 helper waits done (wave 4)
@@ -755,7 +737,6 @@ __global__ __launch_bounds__(512, 1) void stem_roles_kernel(StemArgs a) {
           const uint32_t hbase = lds_addr(hrow) + fq * 2 * kHpCol + (fr >> 3) * 16 + (fr & 7) * 2;
           const uint32_t ebase = lds_addr(erow) + fq * kHpCol + (fr >> 3) * 16 + (fr & 7) * 2;
           uint32_t prevq[2];
-          using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
           // opaque bases, so the compiler does not re-derive (and re-merge)
           // the addresses across K steps / fragments
 #pragma unroll
@@ -828,7 +809,7 @@ __global__ __launch_bounds__(512, 1) void stem_roles_kernel(StemArgs a) {
         }
       }
       if (stp) stp[4 * t + 1] = __builtin_amdgcn_s_memrealtime();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      lgkm_wait();
     } else {
       // DMA the raw rows step t+2's conversion reads: this wave's rows
       // 8t+21+hw and 8t+25+hw, DPR instructions each (rows outside the image
@@ -886,7 +867,7 @@ __global__ __launch_bounds__(512, 1) void stem_roles_kernel(StemArgs a) {
       // step's DMAs and stores (vmcnt retires in issue order)
       if (stp) stp[4 * t + 2] = __builtin_amdgcn_s_memrealtime();
       vm_wait_dyn(nwait);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      lgkm_wait();
       if (stp) stp[4 * t + 3] = __builtin_amdgcn_s_memrealtime();
     }
     __builtin_amdgcn_s_barrier();
