@@ -261,7 +261,7 @@ void bottleneck56_head(const void* x, const void* w1, const float* b1, const voi
 // yd = downsample + bd; wdf = bd = yd = null: the conv alone (the downsample
 // then runs inside conv2: conv3x3_rows28's xds).
 bool conv3x3_s2rows_supported(int Hin, int Win, int Cin, int Cout);
-// ResNet50 layer2.0.conv2, 56x56x128 -> 28x28x128 / s2 (conv3x3_s2rows128.hip):
+// ResNet50 layer2.0.conv2, 56x56x128 -> 28x28x128 / s2 (conv3x3_s2rows.hip, its 128-channel shape):
 // one weight-stationary workgroup per image; wf in fragment order; y bf16, or
 // e4m3 (relu(v) * out_inv_scale) when out_inv_scale > 0.
 bool conv3x3_s2rows128_supported(int Hin, int Win, int Cin, int Cout);

@@ -111,7 +111,7 @@ struct EngineOptions {
   bool stream_l4s2 = true;       // ... also for 14x14x256 -> 512 / s2 (register weights only)
   bool fuse_ds = true;           // the block's 1x1/s2 downsample inside the stride-2 stream conv1
   // ResNet50 layer2.0.conv2 (56x56x128 -> 128 / s2): one weight-stationary
-  // workgroup per image walking its rows (conv3x3_s2rows128.hip), B >= 0.7 x CUs
+  // workgroup per image walking its rows (conv3x3_s2rows.hip, S2Shape128), B >= 0.7 x CUs
   bool s2rows128 = true;
   bool s2rows = true;            // ... layer2.0 (56x56x64 -> 128): one weight-stationary kernel per image
                                  // walking its rows (conv3x3_s2rows.hip), B >= 0.7 x CUs

@@ -250,7 +250,7 @@ def conv3x3_s2rows128(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tenso
                       out_inv_scale: float = 0.0):
     """ResNet50 layer2.0.conv2, [B,56,56,128] -> [B,28,28,128] stride 2, one
     row-streaming weight-stationary workgroup per image
-    (conv3x3_s2rows128.hip). Returns bf16, or e4m3 bytes (uint8) of
+    (conv3x3_s2rows.hip, its 128-channel shape). Returns bf16, or e4m3 bytes (uint8) of
     relu?(conv + bias) * out_inv_scale when out_inv_scale > 0."""
     _need_cuda(x, w_packed, bias)
     C = native()

@@ -515,7 +515,7 @@ def test_conv3x3_s2rows(gpu, B):
 
 @pytest.mark.parametrize("B,out8", [(1, False), (3, False), (2, True)])
 def test_conv3x3_s2rows128(gpu, B, out8):
-    """ResNet50 layer2.0.conv2 row-streaming kernel (conv3x3_s2rows128.hip)
+    """ResNet50 layer2.0.conv2 row-streaming kernel (conv3x3_s2rows.hip, its 128-channel shape)
     vs torch fp32: bf16 output, and e4m3 output (relu(v) * inv_scale,
     dequantised) against the same reference at e4m3 resolution."""
     g = torch.Generator().manual_seed(41 + B)

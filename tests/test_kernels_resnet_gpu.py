@@ -1,5 +1,6 @@
 """Op-level tests of the kernels that carry ResNet18's throughput and query
-paths: conv3x3_rows, conv3x3_s2rows, conv3x3_rows28, conv3x3_stream (stride 1,
+paths: conv3x3_rows, conv3x3_s2rows (with its 128-channel shape, ResNet50's
+conv3x3_s2rows128), conv3x3_rows28, conv3x3_stream (stride 1,
 stride 2 + fused downsample), conv_small, stem_pool (paired bf16 input, and the
 u8 dense-K role-split form) and conv3x3_block.
 
@@ -21,6 +22,8 @@ control ratio and which control), not thresholds:
   conv3x3_rows                 0.92   1132 (border taps)
   conv3x3_s2rows y             0.90   1174 (chunk swap); the conv alone 0.90, 1085
   conv3x3_s2rows yd            0.99   7168 (chunk swap)
+  conv3x3_s2rows128            0.77    594 (border taps)
+  conv3x3_s2rows128 e4m3       0.92    627 (chunk swap)
   conv3x3_rows28               0.83    408 (chunk swap)
   conv3x3_rows28 downsample=   0.80    233 (chunk swap)
   conv3x3_rows28 e4m3          0.92    212 (chunk swap)
@@ -272,6 +275,86 @@ def test_conv3x3_s2rows_bad_args(gpu):
         ops.conv3x3_s2rows(x, wp, b, None, b)
     with pytest.raises(ValueError):
         ops.conv3x3_s2rows(x, wp, b, wdp[:, :32].contiguous(), b)
+    C, P = dmlc.native(), ops._ptr
+    wf, zero = ops.stream_weight_frag(wp), ops._zero_page(gpu)
+    with pytest.raises(ValueError):  # in place
+        C.conv3x3_s2rows(P(x), P(wf), P(b), 0, 0, P(x), 0, P(zero), 1, True, ops._stream())
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------- conv3x3_s2rows128 (ResNet50 layer2.0 conv2)
+S2_128_RING = kb.kernel_const("conv3x3_s2rows.hip", "kRing128")
+
+
+def _controls_s2rows128(ref, x, w, B):
+    ring_row = S2_128_RING // 2  # the first output row whose newest input row, 2 row + 1, is a ring length from row 0
+    return _controls_s2(ref, x, w, B, col=13) + [("ring row", kb.fault_ring_row(ref, x, w, ring_row, S2_128_RING, 2))]
+
+
+@pytest.mark.parametrize("B", [1, 3])
+def test_conv3x3_s2rows128(gpu, B):
+    """The 128-channel shape's bf16 output, K = 1152, with and without ReLU."""
+    x, w, bias = _operands(B, 128, 128, 56, 3, 290 + B)
+    ref, mag = _ref(B, 128, 128, 56, 2, 290 + B)
+    xd, wp, bg = _dev(x, gpu), _pack(w, gpu), bias.float().to(gpu)
+    controls = _controls_s2rows128(ref, x, w, B)
+    for relu in (True, False):
+        y = ops.conv3x3_s2rows128(xd, wp, bg, relu=relu)
+        _check(y, ref, mag, 1152, relu, controls, f"conv3x3_s2rows128 B={B} relu={relu}")
+
+
+def test_conv3x3_s2rows128_e4m3(gpu):
+    """The OUT8 template: e4m3(relu(conv + b) inv_scale), nothing saturating,
+    under conv3x3_rows28's e4m3 bar."""
+    B = 2
+    x, w, bias = _operands(B, 128, 128, 56, 3, 292)
+    ref, mag = _ref(B, 128, 128, 56, 2, 292)
+    r = torch.relu(ref)
+    inv = 400.0 / r.max().item()
+    y8 = ops.conv3x3_s2rows128(_dev(x, gpu), _pack(w, gpu), bias.float().to(gpu), out_inv_scale=inv)
+    assert y8.dtype == torch.uint8 and y8.shape == (B, 28, 28, 128)
+    y = kb.nchw(y8.view(torch.float8_e4m3fn).float().cpu())
+    bnd = kb.e4m3_bound(r, mag, 1152, inv)
+    what = "conv3x3_s2rows128 e4m3"
+    kb.assert_close(y, r * inv, bnd, what, l2=4e-2)  # 2^-4 / sqrt(3) = 3.6e-2: e4m3's own rms roundoff at worst
+    for name, wrong in _controls_s2rows128(ref, x, w, B):
+        kb.assert_rejects(y, torch.relu(wrong) * inv, bnd, f"{what} [{name}]")
+
+
+def test_conv3x3_s2rows128_impulse(gpu):
+    # input rows at the 9-row ring's wrap (row yy in slot (yy + 1) % 9: 7 | 8 early, 43 | 44 and 52 | 53 late); columns
+    # 53, 55 (slots 27, 28: the last odd ones) and 0, 2 (slots 29, 30: the first even ones); (11, 47): output rows 5, 6
+    # x columns 23, 24, row 5 being the second row of its step, pixels 51, 52 of it: live lanes of the clamped 4th
+    # fragment; (53, 55) reaches its last live lane (output (27, 27) too); row and column 55
+    pixels = [(7, 0), (8, 55), (43, 2), (44, 53), (52, 20), (53, 55), (11, 47), (55, 55), (0, 1)]
+    _, w, _ = _operands(1, 128, 128, 56, 3, 291)
+    wp, zero = _pack(w, gpu), torch.zeros(128, device=gpu)
+    _run_impulses(lambda x: ops.conv3x3_s2rows128(x, wp, zero, relu=False), w, pixels, 128, 56, 2, gpu,
+                  "conv3x3_s2rows128")
+
+
+def test_conv3x3_s2rows128_bad_args(gpu):
+    x = torch.zeros(1, 56, 56, 128, dtype=torch.bfloat16, device=gpu)
+    wp = torch.zeros(128, 1152, dtype=torch.bfloat16, device=gpu)
+    b = torch.zeros(128, device=gpu)
+    with pytest.raises(ValueError):  # the 64-channel shape's input
+        ops.conv3x3_s2rows128(x[..., :64].contiguous(), wp, b)
+    with pytest.raises(ValueError):  # wrong weights
+        ops.conv3x3_s2rows128(x, wp[:, :576].contiguous(), b)
+    C, P = dmlc.native(), ops._ptr
+    wf = ops.stream_weight_frag(wp)
+    y = torch.empty(1, 28, 28, 128, dtype=torch.bfloat16, device=gpu)
+    with pytest.raises(ValueError):  # in place
+        C.conv3x3_s2rows128(P(x), P(wf), P(b), P(x), 1, True, 0.0, ops._stream())
+    with pytest.raises(ValueError):  # misaligned
+        C.conv3x3_s2rows128(P(x) + 2, P(wf), P(b), P(y), 1, True, 0.0, ops._stream())
+    with pytest.raises(ValueError):
+        C.conv3x3_s2rows128(P(x), P(wf), P(b), P(y) + 8, 1, True, 0.0, ops._stream())
+    with pytest.raises(ValueError):  # null
+        C.conv3x3_s2rows128(P(x), 0, P(b), P(y), 1, True, 0.0, ops._stream())
+    with pytest.raises(ValueError):  # a batch whose element count overflows int
+        C.conv3x3_s2rows128(P(x), P(wf), P(b), P(y), 5350, True, 0.0, ops._stream())
+    torch.cuda.synchronize()
 
 
 # ---------------------------------------------------------------- conv3x3_rows28 (layer2's stride-1 convs)

@@ -213,107 +213,72 @@ def _s2rows_swz(y, x):
     return ((((y + 1) >> 1) * 28 + ((x + 1) >> 1)) >> 1) & 3
 
 
-def test_s2rows_lds_layout():
-    """conv3x3_s2rows.hip: every ds_read_b128 of a 112-pixel step (7
-    fragments x 9 taps x 2 K halves, all 7 steps, through the 17-row ring
-    with its 2 guard slots) is conflict free and reads the channels the
-    weight fragment expects; the DMA staging order of a row covers every
-    (column, channel chunk) once."""
-    RB, HALF, RING = 7424, 3712, 17
-    # ring contents as (row) per slot, guard slots 17/18 mirroring 0/1
-    for r0 in range(0, 28, 4):
-        sb = (2 * r0) % RING
-        for f in range(7):
+@pytest.mark.parametrize("planes,plane,R,ring", [(2, 58 * 64, 4, 17), (4, 57 * 64, 2, 9)], ids=["ci64", "ci128"])
+def test_s2rows_lds_layout(planes, plane, R, ring):
+    """conv3x3_s2rows.hip, both shapes (ci64: ResNet18 layer2.0.conv1, 2
+    K-half planes of 58 slots, 4 output rows per step, 17-row ring; ci128:
+    ResNet50 layer2.0.conv2, 4 channel-quarter planes of 57 slots, 2 rows per
+    step, 9-row ring): every ds_read_b128 of a step (ceil(28 R / 16)
+    fragments, the lanes of a partial last fragment clamped to the step's
+    last pixel; 9 taps x planes; all 28 / R steps, through the ring with its
+    2 guard slots) is conflict free and reads the channels the weight
+    fragment expects; the rows in use and in flight never share a ring slot;
+    the DMA staging order of a row covers every (column, channel chunk) once
+    and leaves exactly the pad and spare slots alone; the ring fits the LDS."""
+    RB = planes * plane
+    npix = R * 28
+    assert ring == 4 * R + 1 and 28 % R == 0
+    assert RB % 256 == 0 and (ring + 2) * RB <= 160 * 1024
+    for r0 in range(0, 28, R):
+        sb = (2 * r0) % ring
+        for f in range((npix + 15) // 16):
             for kh in range(3):
                 for kw in range(3):
-                    for h in range(2):
+                    for q in range(planes):
                         addr = []
                         for l in range(64):
                             fr, g = l & 15, l >> 4
-                            p = 16 * f + fr
+                            p = min(16 * f + fr, npix - 1)
                             r, c = r0 + p // 28, p % 28
                             y, x = 2 * r + kh - 1, 2 * c + kw - 1
                             sl = sb + 2 * (p // 28)
-                            sl = sl - RING if sl >= RING else sl
+                            sl = sl - ring if sl >= ring else sl
                             # kernel: rowoff + col[v] + immediate
                             v = (kw == 2) + 2 * (kh == 2)
                             s = ((p + (v & 1) + 28 * (v >> 1)) >> 1) & 3
                             col = (c + (v & 1)) * 64 + ((g ^ s) << 4)
-                            a = sl * RB + col + kh * RB + (29 * 64 if kw == 1 else 0) + h * HALF
+                            a = sl * RB + col + kh * RB + (29 * 64 if kw == 1 else 0) + q * plane
                             addr.append(a)
-                            # the slot holds row y (mod the ring, guards mirror slots 0/1)
+                            # the slot holds row y (mod the ring, guards mirror slots 0 / 1)
                             slot = a // RB
-                            assert (slot % RING) == (y + 1) % RING and slot < RING + 2
+                            assert slot < ring + 2 and (slot % ring) == (y + 1) % ring
+                            if y < 0:
+                                assert slot == 0 and r0 == 0  # the zero row (step 0 only)
                             off = a % RB
-                            hh, j = off // HALF, off % HALF
-                            assert hh == h and j // 64 == _s2rows_pos(x)
-                            # stored chunk holds logical chunk 4h + (phys ^ swz(y, x)) == 4h + g
+                            qq, j = off // plane, off % plane
+                            assert qq == q and j // 64 == _s2rows_pos(x)
+                            # stored chunk holds logical chunk 4q + (phys ^ swz(y, x)) == 4q + g
                             assert ((j % 64) // 16) ^ _s2rows_swz(y, x) == g
-                        assert _b128_ways(addr) == 1, (r0, f, kh, kw, h)
+                        assert _b128_ways(addr) == 1, (r0, f, kh, kw, q)
+    # rows in use at a step (2 r0 - 1 .. 2 r0 + 2R - 1) and those DMA'd during it
+    # (2 r0 + 2R .. 2 r0 + 4R - 1) occupy `ring` distinct slots
+    for r0 in range(0, 28 - R, R):
+        assert len({(yy + 1) % ring for yy in range(2 * r0 - 1, 2 * r0 + 4 * R)}) == ring
     seen, dst = set(), set()
-    for h in range(2):  # load_row: chunk k of K-half h's run -> LDS chunk, source column / channel chunk
+    for q in range(planes):  # load_row: chunk k of plane q's run -> LDS chunk, source column / channel chunk
         for k in range(224):
             pos, c = 1 + k // 4, k % 4
             x = 2 * pos - 1 if pos < 29 else 2 * (pos - 29)
             assert _s2rows_pos(x) == pos
-            dst.add(h * HALF // 16 + 4 + k)
-            seen.add((x, 4 * h + (c ^ _s2rows_swz(0, x))))
-    assert seen == {(x, cc) for x in range(56) for cc in range(8)}
-    # the chunks never DMA'd (pad slot 0 and spare slot 57 of each plane) stay zero
-    assert {i for i in range(RB // 16) if i not in dst} == {h * HALF // 16 + j for h in range(2) for j in (0, 1, 2, 3, 228, 229, 230, 231)}
-
-
-def test_s2rows128_lds_layout():
-    """conv3x3_s2rows128.hip (ResNet50 layer2.0.conv2): every ds_read_b128 of
-    a 2-row step (4 fragments, the last 8 lanes clamped to pixel 55; 9 taps x
-    4 channel quarters; all 14 steps through the 9-row ring and its 2 guard
-    slots) is conflict free and reads the channels the weight fragment
-    expects; the DMA order of a row covers every (column, channel chunk) once;
-    the ring fits the LDS."""
-    PLANE, RING = 57 * 64, 9
-    RB = 4 * PLANE
-    assert RB % 256 == 0 and (RING + 2) * RB <= 160 * 1024
-    for r0 in range(0, 28, 2):
-        sb = (2 * r0) % RING
-        for f in range(4):
-            for kh in range(3):
-                for kw in range(3):
-                    for q in range(4):
-                        addr = []
-                        for l in range(64):
-                            fr, g = l & 15, l >> 4
-                            p = min(16 * f + fr, 55)
-                            r, c = r0 + p // 28, p % 28
-                            y, x = 2 * r + kh - 1, 2 * c + kw - 1
-                            sl = sb + 2 * (p // 28)
-                            sl = sl - RING if sl >= RING else sl
-                            v = (kw == 2) + 2 * (kh == 2)
-                            s = ((p + (v & 1) + 28 * (v >> 1)) >> 1) & 3
-                            col = (c + (v & 1)) * 64 + ((g ^ s) << 4)
-                            a = sl * RB + col + kh * RB + (29 * 64 if kw == 1 else 0) + q * PLANE
-                            addr.append(a)
-                            slot = a // RB
-                            assert slot < RING + 2
-                            if y >= 0:
-                                assert (slot % RING) == (y + 1) % RING
-                            else:
-                                assert slot == 0  # the zero row (step 0 only)
-                            off = a % RB
-                            qq, j = off // PLANE, off % PLANE
-                            assert qq == q and j // 64 == _s2rows_pos(x)
-                            assert ((j % 64) // 16) ^ _s2rows_swz(y, x) == g
-                        assert _b128_ways(addr) == 1, (r0, f, kh, kw, q)
-    # rows in use at a step (2 r0 - 1 .. 2 r0 + 3) and those DMA'd during it
-    # (2 r0 + 4 .. 2 r0 + 7) occupy 9 distinct slots
-    for r0 in range(0, 26, 2):
-        assert len({(yy + 1) % RING for yy in range(2 * r0 - 1, 2 * r0 + 8)}) == 9
-    seen = set()
-    for q in range(4):
-        for k in range(224):
-            pos, c = 1 + k // 4, k % 4
-            x = 2 * pos - 1 if pos < 29 else 2 * (pos - 29)
+            assert (q * plane // 16 + 4 + k) not in dst
+            dst.add(q * plane // 16 + 4 + k)
+            assert (x, 4 * q + (c ^ _s2rows_swz(0, x))) not in seen
             seen.add((x, 4 * q + (c ^ _s2rows_swz(0, x))))
-    assert seen == {(x, cc) for x in range(56) for cc in range(16)}
+    assert seen == {(x, cc) for x in range(56) for cc in range(4 * planes)}
+    # the chunks never DMA'd (pad slot 0 and the spare slots past 56 of each plane) stay zero
+    spare = range(228, plane // 16)
+    assert {i for i in range(RB // 16) if i not in dst} == {q * plane // 16 + j for q in range(planes)
+                                                            for j in (0, 1, 2, 3, *spare)}
 
 
 def test_rows28_lds_layout():
