@@ -13,6 +13,7 @@
 
 #include "../kernels/kernels.h"
 #include "../runtime/engine.h"
+#include "../runtime/gallery.h"
 #include "../runtime/jpeg.h"
 #include "../runtime/jpeg_gpu.h"
 #include "../runtime/ot_io.h"
@@ -464,6 +465,51 @@ PYBIND11_MODULE(_C, m) {
     embed_rows(P<void>(x), P<float>(out), B, HW, C, in_fp8, scale, l2norm, S(stream));
   }, py::arg("x"), py::arg("out"), py::arg("B"), py::arg("HW"), py::arg("C"), py::arg("in_fp8"), py::arg("scale"),
         py::arg("l2norm"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  // nearest-neighbour search (sim_topk.hip); the sizing functions need no device
+  m.def("sim_topk_supported", &sim_topk_supported, py::arg("D"));
+  m.def("sim_topk_slices", &sim_topk_slices, py::arg("B"), py::arg("N"), py::arg("num_cus"));
+  m.def("sim_topk_max_slices", &sim_topk_max_slices, py::arg("N"));
+  m.def("sim_topk_slice_rows", [](long N, int slices, int slice) {
+    long first = 0, end = 0;
+    sim_topk_slice_rows(N, slices, slice, &first, &end);
+    return py::make_tuple(first, end);
+  }, py::arg("N"), py::arg("slices"), py::arg("slice"));
+  m.def("sim_topk_ws_bytes", &sim_topk_ws_bytes, py::arg("B"), py::arg("k"), py::arg("slices"));
+  m.def("sim_topk", [](uintptr_t q, TensorDType qdt, uintptr_t q_scale, uintptr_t g, uintptr_t g_scale, int B, long N,
+                       int D, int k, uintptr_t idx, uintptr_t score, uintptr_t ws, size_t ws_bytes, int num_cus,
+                       uintptr_t stream, int slices) {
+    sim_topk(P<void>(q), qdt, P<float>(q_scale), P<void>(g), P<float>(g_scale), B, N, D, k, P<int32_t>(idx),
+             P<float>(score), P<void>(ws), ws_bytes, num_cus, S(stream), slices);
+  }, py::arg("q"), py::arg("dtype"), py::arg("q_scale"), py::arg("g"), py::arg("g_scale"), py::arg("B"), py::arg("N"),
+        py::arg("D"), py::arg("k"), py::arg("idx"), py::arg("score"), py::arg("ws"), py::arg("ws_bytes"),
+        py::arg("num_cus"), py::arg("stream"), py::arg("slices") = 0, py::call_guard<py::gil_scoped_release>());
+  m.def("gallery_pack", [](uintptr_t rows, uintptr_t g, uintptr_t inv_norm, int M, int D, uintptr_t stream) {
+    gallery_pack(P<float>(rows), P<void>(g), P<float>(inv_norm), M, D, S(stream));
+  }, py::arg("rows"), py::arg("g"), py::arg("inv_norm"), py::arg("M"), py::arg("D"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  py::class_<Gallery>(m, "Gallery")
+      .def(py::init([](int dim, long capacity, int device, const std::string& metric, int max_batch) {
+             if (metric != "cosine" && metric != "dot")
+               throw std::invalid_argument("Gallery: metric is \"cosine\" or \"dot\", got " + metric);
+             return new Gallery(dim, capacity, device, metric == "cosine", max_batch);
+           }),
+           py::arg("dim"), py::arg("capacity"), py::arg("device") = 0, py::arg("metric") = "cosine",
+           py::arg("max_batch") = 256)
+      .def_property_readonly("dim", &Gallery::dim)
+      .def_property_readonly("capacity", &Gallery::capacity)
+      .def_property_readonly("device", &Gallery::device)
+      .def_property_readonly("max_batch", &Gallery::max_batch)
+      .def_property_readonly("size", &Gallery::size)
+      .def_property_readonly("metric", [](const Gallery& g) { return std::string(g.cosine() ? "cosine" : "dot"); })
+      .def("add", [](Gallery& g, uintptr_t rows, int M, uintptr_t stream) { return g.add(P<float>(rows), M, S(stream)); },
+           py::arg("rows"), py::arg("M"), py::arg("stream"), py::call_guard<py::gil_scoped_release>())
+      .def("search",
+           [](Gallery& g, uintptr_t q, TensorDType qdt, int B, int k, uintptr_t idx, uintptr_t score, uintptr_t stream) {
+             g.search(P<void>(q), qdt, B, k, P<int32_t>(idx), P<float>(score), S(stream));
+           },
+           py::arg("q"), py::arg("dtype"), py::arg("B"), py::arg("k"), py::arg("idx"), py::arg("score"),
+           py::arg("stream"), py::call_guard<py::gil_scoped_release>())
+      .def("clear", &Gallery::clear);
 
   // ---------------------------------------------------------------- jpeg
   m.def("decode_jpeg", [](py::bytes data) {

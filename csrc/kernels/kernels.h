@@ -459,4 +459,36 @@ bool embed_rows_supported(int HW, int C);  // HW >= 1, C % 8 == 0, C <= 8192
 void embed_rows(const void* x, float* out, int B, int HW, int C, bool in_fp8, float scale, bool l2norm,
                 hipStream_t s);
 
+// Nearest-neighbour search (sim_topk.hip): row b of idx / score holds the
+// rows n and scores of the k largest
+//   score(b, n) = (sum_d bf16(q[b][d]) g[n][d]) q_scale[b] g_scale[n]
+// over n = 0..N-1, in descending order, equal scores by ascending n
+// (softmax_topk's tie rule). Exact products, fp32 accumulation over the whole
+// of D by one wave in one K order, then the two fp32 multiplies in that order
+// (a null scale is 1): a score's bits do not depend on B, N, the row's place
+// or the slice count. q: fp32 (rounded to bf16, nearest even) or bf16 [B, D];
+// g: bf16 [N, D]; q, g and ws 16-B aligned. 1 <= k <= min(N, kMaxTopK),
+// N < 2^31; the inputs are assumed finite. The gallery is cut into `slices`
+// contiguous runs of whole 128-row tiles (sim_topk_slices: about one
+// workgroup per CU, at most sim_topk_max_slices), merged by a second kernel
+// when there is more than one; blocks of 256 queries are separate launches.
+// ws: sim_topk_ws_bytes(B, k, slices) bytes, no initial contents needed.
+bool sim_topk_supported(int D);  // D % 32 == 0, 32 <= D <= 4096
+int sim_topk_slices(int B, long N, int num_cus);
+int sim_topk_max_slices(long N);  // min(tiles, 512)
+// rows [*first, *end) of slice `slice` of `slices`
+void sim_topk_slice_rows(long N, int slices, int slice, long* first, long* end);
+size_t sim_topk_ws_bytes(int B, int k, int slices);
+void sim_topk(const void* q, TensorDType qdt /*F32 or BF16*/, const float* q_scale /*[B] or null*/,
+              const void* g /*bf16 [N, D]*/, const float* g_scale /*[N] or null*/, int B, long N, int D, int k,
+              int32_t* idx /*[B,k]*/, float* score /*[B,k]*/, void* ws, size_t ws_bytes, int num_cus, hipStream_t s,
+              int slices_override = 0);
+// fp32 rows [M, D] -> bf16 (nearest even) g [M, D]; inv_norm (or null): [M],
+// 1 / max(sqrt(sum v^2), 1e-12) of the rounded values v, summed in fp32:
+// embed_rows' normalisation rule on what the MFMA reads. D % 8 == 0,
+// D <= 8192; rows and g 16-B aligned.
+void gallery_pack(const float* rows, void* g, float* inv_norm, int M, int D, hipStream_t s);
+// the same inverse norms of rows that are bf16 already
+void gallery_inv_norms(const void* rows_bf16, float* inv_norm, int M, int D, hipStream_t s);
+
 }  // namespace dmlc

@@ -27,3 +27,11 @@ def native():
     import importlib
     import torch  # noqa: F401
     return importlib.import_module(__name__ + "._C")
+
+
+def __getattr__(name):
+    """``dmlc.Gallery`` (gallery.py), imported on first use: it needs torch."""
+    if name == "Gallery":
+        import importlib
+        return importlib.import_module(__name__ + ".gallery").Gallery
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -948,6 +948,100 @@ def embed_rows(x: torch.Tensor, normalize: bool = False, scale: float | None = N
     return out
 
 
+# ---------------------------------------------------------------- nearest-neighbour search
+_SIM_WS: dict = {}
+
+
+def _sim_ws(device: torch.device, nbytes: int) -> torch.Tensor:
+    """Per-device search workspace, grown on demand (no initial contents needed)."""
+    t = _SIM_WS.get(device.index)
+    if t is None or t.numel() < nbytes:
+        if t is not None:
+            torch.cuda.synchronize(device)
+        t = _SIM_WS[device.index] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return t
+
+
+def query_rows(q: torch.Tensor, dim: int | None, device, what: str):
+    """Check search queries: contiguous float32 / bfloat16 [B, dim] on ``device``. Returns the native dtype."""
+    if q.dtype not in (torch.float32, torch.bfloat16) or q.dim() != 2 or (dim is not None and q.shape[1] != dim) \
+            or q.device != device or not q.is_contiguous():
+        raise ValueError(f"{what}: expected contiguous float32 / bfloat16 [B,{dim if dim is not None else 'D'}] on "
+                         f"{device}, got {q.dtype} {tuple(q.shape)} (strides {tuple(q.stride())}) on {q.device}")
+    return getattr(native().TensorDType, _TENSOR_DTYPES[q.dtype])
+
+
+def topk_out(out, B: int, k: int, device, what: str):
+    """The (idx int32 [B,k], score float32 [B,k]) pair of a search: ``out`` checked, or new tensors."""
+    if out is None:
+        return (torch.empty(B, k, dtype=torch.int32, device=device),
+                torch.empty(B, k, dtype=torch.float32, device=device))
+    idx, score = out
+    for t, dt in ((idx, torch.int32), (score, torch.float32)):
+        if t.device != device or t.dtype != dt or tuple(t.shape) != (B, k) or not t.is_contiguous():
+            raise ValueError(f"{what}: out expects contiguous {dt} [{B},{k}] on {device}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    return idx, score
+
+
+def sim_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, q_scale: torch.Tensor | None = None,
+             g_scale: torch.Tensor | None = None, out=None, slices: int | None = None):
+    """The k gallery rows nearest to each query (csrc/kernels/sim_topk.hip):
+    (idx int32 [B,k], score f32 [B,k]), score(b, n) = (sum_d bf16(q[b,d])
+    g[n,d]) q_scale[b] g_scale[n] in descending order, equal scores by
+    ascending n. queries: float32 (rounded to bf16) or bfloat16 [B,D];
+    gallery: bfloat16 [N,D], D % 32 == 0, 32 <= D <= 4096; the scales:
+    float32 [B] / [N] or None (1). 1 <= k <= min(N, MAX_TOPK). ``out``: the
+    (idx, score) pair to write; ``slices``: how many runs of whole 128-row
+    tiles the gallery is cut into (default: about one per CU) - the answer's
+    bits do not depend on it."""
+    _need_cuda(queries, gallery, q_scale, g_scale)
+    C = native()
+    dev = gallery.device
+    if gallery.dtype != torch.bfloat16 or gallery.dim() != 2 or not gallery.is_contiguous():
+        raise ValueError(f"sim_topk: gallery must be contiguous bfloat16 [N,D], got {gallery.dtype} "
+                         f"{tuple(gallery.shape)}")
+    N, D = gallery.shape
+    if not C.sim_topk_supported(D):
+        raise ValueError(f"sim_topk: needs D % 32 == 0 and 32 <= D <= 4096, got D = {D}")
+    qdt = query_rows(queries, D, dev, "sim_topk")
+    B = queries.shape[0]
+    if not isinstance(k, int) or not 1 <= k <= min(N, C.MAX_TOPK):
+        raise ValueError(f"sim_topk: k = {k} outside 1..min(N = {N}, {C.MAX_TOPK})")
+    for t, n, what in ((q_scale, B, "q_scale"), (g_scale, N, "g_scale")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (n,) or t.device != dev
+                              or not t.is_contiguous()):
+            raise ValueError(f"sim_topk: {what} must be contiguous float32 [{n}] on {dev}")
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    if slices is None:
+        slices = C.sim_topk_slices(B, N, cus)
+    elif not isinstance(slices, int) or not 1 <= slices <= C.sim_topk_max_slices(N):
+        raise ValueError(f"sim_topk: slices = {slices} outside 1..{C.sim_topk_max_slices(N)}")
+    idx, score = topk_out(out, B, k, dev, "sim_topk")
+    if B == 0:
+        return idx, score
+    ws = _sim_ws(dev, C.sim_topk_ws_bytes(B, k, slices))
+    C.sim_topk(_ptr(queries), qdt, _ptr(q_scale), _ptr(gallery), _ptr(g_scale), B, N, D, k, _ptr(idx), _ptr(score),
+               _ptr(ws), ws.numel(), cus, _stream(), slices=slices)
+    return idx, score
+
+
+def gallery_pack(rows: torch.Tensor, with_norms: bool = False):
+    """float32 rows [M,D] -> bfloat16 [M,D] (nearest even), as a gallery stores
+    them; with_norms: also float32 [M], 1 / max(sqrt(sum v^2), 1e-12) of the
+    rounded values v (the cosine metric's scales). D % 8 == 0, D <= 8192."""
+    _need_cuda(rows)
+    if rows.dtype != torch.float32 or rows.dim() != 2 or not rows.is_contiguous():
+        raise ValueError(f"gallery_pack expects contiguous float32 [M,D], got {rows.dtype} {tuple(rows.shape)}")
+    M, D = rows.shape
+    if D < 8 or D % 8 or D > 8192:
+        raise ValueError(f"gallery_pack: needs D % 8 == 0 and 8 <= D <= 8192, got D = {D}")
+    g = torch.empty(M, D, dtype=torch.bfloat16, device=rows.device)
+    inv = torch.empty(M, dtype=torch.float32, device=rows.device) if with_norms else None
+    native().gallery_pack(_ptr(rows), _ptr(g), _ptr(inv), M, D, _stream())
+    return (g, inv) if with_norms else g
+
+
 # ---------------------------------------------------------------- split JPEG decode
 def _align(n: int, a: int = 256) -> int:
     return (n + a - 1) // a * a

@@ -48,6 +48,7 @@ class InferenceEngine:
         # length of the vector the last fc reads: 512 (ResNet18/34), 2048 (ResNet50), 4096 (AlexNet)
         self.feature_dim = self._e.feature_dim
         self._scratch = None  # embed(): idx / prob nobody reads
+        self._features = None  # index() / search(): the embeddings on their way to a gallery
 
     @property
     def gflop_per_image(self) -> float:
@@ -99,6 +100,35 @@ class InferenceEngine:
                              torch.empty(self.max_batch, dtype=torch.float32, device=self.device))
         answer = (self._scratch[0][:B], self._scratch[1][:B])
         return self._predict(images, use_graph, answer, False, 1, (out, bool(normalize)))[-1]
+
+    def _check_gallery(self, gallery, what: str) -> None:
+        if getattr(gallery, "dim", None) != self.feature_dim or getattr(gallery, "device", None) != self.device:
+            raise ValueError(f"{what}: expected a dmlc.Gallery of dim {self.feature_dim} on {self.device}, got dim "
+                             f"{getattr(gallery, 'dim', None)} on {getattr(gallery, 'device', None)}")
+
+    def index(self, images: torch.Tensor, gallery, use_graph: bool = True) -> range:
+        """``gallery.add(self.embed(images))``: store the images' embeddings
+        in a ``dmlc.Gallery`` of this engine's ``feature_dim`` on this GPU;
+        the new rows' ids. images as for ``predict``."""
+        self._check_gallery(gallery, "index")
+        return gallery.add(self._embed_into_buffer(images, use_graph))
+
+    def search(self, images: torch.Tensor, gallery, k: int = 1, use_graph: bool = True, out=None):
+        """The k stored rows nearest to each image: ``gallery.search(
+        self.embed(images), k)``, the same bits, with the embeddings in a
+        buffer the engine keeps and the search launched on the same stream
+        after the forward (whose plan and graphs are what ``embed`` uses).
+        Returns (idx int32 [B,k], score f32 [B,k])."""
+        self._check_gallery(gallery, "search")
+        return gallery.search(self._embed_into_buffer(images, use_graph), k, out)
+
+    def _embed_into_buffer(self, images, use_graph):
+        B = images.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f"{B} images exceed max_batch = {self.max_batch}")
+        if self._features is None:
+            self._features = torch.empty(self.max_batch, self.feature_dim, dtype=torch.float32, device=self.device)
+        return self.embed(images, use_graph=use_graph, out=self._features[:B])
 
     def _predict(self, images, use_graph, out, return_logits, topk, feats):
         """feats: None, or (features buffer or None for a new one, normalise)."""

@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""Measurements for the nearest-neighbour search (csrc/kernels/sim_topk.hip,
+dmlc.Gallery, InferenceEngine.search), written as plain text. One GPU.
+
+  kernel  ops-level sim_topk (the native launcher on preallocated outputs) at
+          D = 512, N = 10 k / 100 k / 1 M, B = 1 / 256, k = 1 / 16, dot and
+          cosine, and one row at D = 2048, on bf16 randn; next to it torch on
+          the same GPU in the same run, (q.bfloat16() @ g.T).float().topk(k),
+          the two interleaved block by block after a warm-up that also primes
+          the clocks. Device events around blocks of back-to-back launches;
+          median (min - max) over the blocks. Per row: us per launch, gallery
+          bytes / time against the 8 TB/s HBM peak, issued 2 B N D flop / time
+          against the 2.5 PF bf16 peak.
+  engine  a graph-replayed ResNet18 b256 embed() alone and engine.search()
+          against a 100 k gallery (the same forward, then the search on the
+          same stream), interleaved.
+
+usage: python tools/search_bench.py [kernel] [engine] [--blocks 5] [--out profiles/search.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+import dmlc  # noqa: E402
+from dmlc import ops  # noqa: E402
+
+HBM_PEAK, BF16_PEAK = 8e12, 2.5e15
+
+
+def _block_us(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3
+
+
+def _interleaved(fns, blocks, target_us=30e3):
+    """{name: fn} -> {name: [us per call, one per block]}: warm-up, iterations sized for ~30 ms blocks, turns."""
+    iters = {}
+    for name, fn in fns.items():
+        fn()
+        torch.cuda.synchronize()
+        iters[name] = int(min(500, max(3, target_us / max(_block_us(fn, 3), 1.0))))
+        _block_us(fn, iters[name])
+    times = {name: [] for name in fns}
+    for _ in range(blocks):
+        for name, fn in fns.items():
+            times[name].append(_block_us(fn, iters[name]))
+    return times
+
+
+def _fmt(ts):
+    return f"{statistics.median(ts):9.1f} us ({min(ts):.1f} - {max(ts):.1f})"
+
+
+def bench_kernel(a, emit):
+    dev = torch.device("cuda", 0)
+    C = dmlc.native()
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    stream = torch.cuda.current_stream().cuda_stream
+    emit(f"kernel ({torch.cuda.get_device_name(0)}, {cus} CUs), bf16 randn, native launcher on preallocated outputs "
+         f"vs torch (q.bfloat16() @ g.T).float().topk(k); device events around back-to-back launches, median "
+         f"(min - max) of {a.blocks} interleaved blocks; TB/s = gallery bytes / time (peak 8), TF/s = 2 B N D / time "
+         f"(peak 2500):")
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for D, N in ((512, 10_000), (512, 100_000), (512, 1_000_000), (2048, 100_000)):
+        g32 = torch.randn(N, D, device=dev, generator=gen)
+        g, ginv = ops.gallery_pack(g32, with_norms=True)
+        del g32
+        for B in (1, 256):
+            q = torch.randn(B, D, device=dev, generator=gen)
+            qb, qinv = ops.gallery_pack(q, with_norms=True)
+            for k in (1, 16):
+                if D == 2048 and (B, k) != (256, 16):
+                    continue
+                slices = C.sim_topk_slices(B, N, cus)
+                ws = torch.empty(C.sim_topk_ws_bytes(B, k, slices), dtype=torch.uint8, device=dev)
+                idx = torch.empty(B, k, dtype=torch.int32, device=dev)
+                score = torch.empty(B, k, dtype=torch.float32, device=dev)
+                BF = C.TensorDType.BF16
+
+                def run(qs, gs):
+                    C.sim_topk(qb.data_ptr(), BF, qs, g.data_ptr(), gs, B, N, D, k, idx.data_ptr(), score.data_ptr(),
+                               ws.data_ptr(), ws.numel(), cus, stream)
+                fns = {"dot": lambda: run(0, 0), "cosine": lambda: run(qinv.data_ptr(), ginv.data_ptr()),
+                       "torch": lambda: (qb @ g.t()).float().topk(k)}
+                run(0, 0)
+                ti = (qb @ g.t()).float().topk(k).indices
+                agree = (idx.long() == ti).float().mean().item()
+                t = _interleaved(fns, a.blocks)
+                for name in ("dot", "cosine"):
+                    m = statistics.median(t[name]) * 1e-6
+                    emit(f"  D={D:<5} N={N:<8} B={B:<4} k={k:<3} {name:<7} {_fmt(t[name])}  "
+                         f"{N * D * 2 / m / 1e12:6.3f} TB/s ({N * D * 2 / m / HBM_PEAK * 100:5.1f} %)  "
+                         f"{2.0 * B * N * D / m / 1e12:7.1f} TF/s ({2.0 * B * N * D / m / BF16_PEAK * 100:5.2f} %)  "
+                         f"slices {slices}")
+                mt = statistics.median(t["torch"])
+                emit(f"  {'':<38} torch   {_fmt(t['torch'])}  = {mt / statistics.median(t['dot']):.2f} x the dot "
+                     f"kernel's time; {agree * 100:.1f} % of its (bf16-rounded scores') indices equal the kernel's")
+        del g, ginv
+
+
+def bench_engine(a, emit):
+    from dmlc.models.calibrated import mixed_images
+    from dmlc.runtime import InferenceEngine
+    dev = torch.device("cuda", 0)
+    B, N = 256, 100_000
+    eng = InferenceEngine("resnet18", None, max_batch=B)
+    img = mixed_images(B, seed=1).to(dev)
+    gal = dmlc.Gallery(eng.feature_dim, N, max_batch=B)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    for i in range(0, N, 10_000):
+        gal.add(torch.randn(10_000, eng.feature_dim, device=dev, generator=gen).abs())
+    feats = torch.empty(B, eng.feature_dim, device=dev)
+    out = (torch.empty(B, 16, dtype=torch.int32, device=dev), torch.empty(B, 16, device=dev))
+    fns = {"embed": lambda: eng.embed(img, out=feats), "search": lambda: eng.search(img, gal, k=16, out=out)}
+    t = _interleaved(fns, a.blocks)
+    me, ms = statistics.median(t["embed"]), statistics.median(t["search"])
+    emit(f"engine ({torch.cuda.get_device_name(0)}), resnet18 b{B} graph replay, gallery of {N} x {eng.feature_dim} "
+         f"(cosine, k = 16), median (min - max) of {a.blocks} interleaved blocks:")
+    emit(f"  embed()                 {_fmt(t['embed'])} per batch  {B / me * 1e6:9.0f} images/s")
+    emit(f"  search() = embed+search {_fmt(t['search'])} per batch  {B / ms * 1e6:9.0f} images/s")
+    emit(f"  added by the search     {ms - me:9.1f} us = {(ms - me) / me * 100:.1f} % of the forward")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", nargs="*", default=["kernel", "engine"], help="kernel, engine")
+    ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("search_bench: no GPU visible")
+    lines = []
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    for w in a.what:
+        if w == "kernel":
+            bench_kernel(a, emit)
+        elif w == "engine":
+            bench_engine(a, emit)
+        else:
+            raise SystemExit(f"unknown measurement: {w}")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
