@@ -668,12 +668,33 @@ PYBIND11_MODULE(_C, m) {
                           int B, bool native, int num_cus, int num_classes, int image_size, int topk,
                           bool tensor_in, bool features) {
     std::vector<Op> ops;
-    const auto lines = Engine::plan_audit(arch, to_weight_map(weights), engine_options(options), B, native, num_cus,
-                                          &ops, num_classes, image_size, topk, tensor_in, features);
+    const EngineOptions opt = engine_options(options);
+    PlanSpec spec;
+    spec.B = B, spec.native = native, spec.side = opt.fork_ds;
+    spec.topk = topk, spec.tensor_in = tensor_in, spec.features = features;
+    const auto lines = Engine::plan_audit(arch, to_weight_map(weights), opt, spec, num_cus, &ops, num_classes, image_size);
     return py::make_tuple(plan_list(lines), op_list(ops));
   }, py::arg("arch"), py::arg("weights"), py::arg("options") = std::map<std::string, bool>{}, py::arg("B") = 256,
      py::arg("native") = true, py::arg("num_cus") = 256, py::arg("num_classes") = 1000, py::arg("image_size") = 224,
      py::arg("topk") = 1, py::arg("tensor_in") = false, py::arg("features") = false);
+  auto request = [](uintptr_t data, int B, int Hin, int Win, int k, uintptr_t idx, uintptr_t prob, uintptr_t logits,
+                    uintptr_t features, bool l2norm, bool tensor = false, TensorDType dt = TensorDType::F32,
+                    bool channels_last = false) {
+    return Engine::Request{Engine::Input{P<void>(data), Hin, Win, tensor, dt, channels_last}, B, k, P<int32_t>(idx),
+                           P<float>(prob), P<float>(logits), P<float>(features), l2norm};
+  };
+  // what tells one captured graph from another (Engine::key_of), as ints; no engine, no device
+  m.def("graph_key", [=](uintptr_t images, int B, int Hin, int Win, int k, uintptr_t idx, uintptr_t prob,
+                         uintptr_t logits, uintptr_t features, bool l2norm,
+                         const std::optional<std::pair<TensorDType, bool>>& tensor) {
+    const Engine::GraphKey key = Engine::key_of(
+        tensor ? request(images, B, Hin, Win, k, idx, prob, logits, features, l2norm, true, tensor->first, tensor->second)
+               : request(images, B, Hin, Win, k, idx, prob, logits, features, l2norm));
+    auto U = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    return py::make_tuple(U(key.data), key.B, key.Hin, key.Win, U(key.idx), U(key.prob), U(key.logits), key.k,
+                          key.input_kind, U(key.features), (int)key.l2norm);
+  }, py::arg("images"), py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("k"), py::arg("idx"), py::arg("prob"),
+     py::arg("logits"), py::arg("features") = (uintptr_t)0, py::arg("l2norm") = false, py::arg("tensor") = py::none());
   py::class_<Engine>(m, "Engine")
       .def(py::init([](const std::string& arch, const py::dict& weights, int device, int num_classes,
                        int image_size, const std::map<std::string, bool>& options) {
@@ -692,20 +713,18 @@ PYBIND11_MODULE(_C, m) {
       .def("reserve", &Engine::reserve, py::call_guard<py::gil_scoped_release>())
       .def(
           "forward",
-          [](Engine& e, uintptr_t images, int B, int Hin, int Win, uintptr_t idx, uintptr_t prob,
-             uintptr_t logits, uintptr_t stream, bool use_graph) {
-            e.forward(P<uint8_t>(images), B, Hin, Win, P<int32_t>(idx), P<float>(prob), P<float>(logits),
-                      S(stream), use_graph);
+          [=](Engine& e, uintptr_t images, int B, int Hin, int Win, uintptr_t idx, uintptr_t prob,
+              uintptr_t logits, uintptr_t stream, bool use_graph) {
+            e.forward(request(images, B, Hin, Win, 1, idx, prob, logits, 0, false), S(stream), use_graph);
           },
           py::arg("images"), py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("idx"),
           py::arg("prob"), py::arg("logits"), py::arg("stream"), py::arg("use_graph") = true,
           py::call_guard<py::gil_scoped_release>())
       .def(
           "forward_topk",
-          [](Engine& e, uintptr_t images, int B, int Hin, int Win, int k, uintptr_t idx, uintptr_t prob,
-             uintptr_t logits, uintptr_t stream, bool use_graph, uintptr_t features, bool l2norm) {
-            e.forward_topk(P<uint8_t>(images), B, Hin, Win, k, P<int32_t>(idx), P<float>(prob), P<float>(logits),
-                           S(stream), use_graph, P<float>(features), l2norm);
+          [=](Engine& e, uintptr_t images, int B, int Hin, int Win, int k, uintptr_t idx, uintptr_t prob,
+              uintptr_t logits, uintptr_t stream, bool use_graph, uintptr_t features, bool l2norm) {
+            e.forward(request(images, B, Hin, Win, k, idx, prob, logits, features, l2norm), S(stream), use_graph);
           },
           py::arg("images"), py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("k"), py::arg("idx"),
           py::arg("prob"), py::arg("logits"), py::arg("stream"), py::arg("use_graph") = true,
@@ -713,10 +732,10 @@ PYBIND11_MODULE(_C, m) {
           py::call_guard<py::gil_scoped_release>())
       .def(
           "forward_tensor",
-          [](Engine& e, uintptr_t x, TensorDType dt, bool channels_last, int B, int k, uintptr_t idx, uintptr_t prob,
-             uintptr_t logits, uintptr_t stream, bool use_graph, uintptr_t features, bool l2norm) {
-            e.forward_tensor(P<void>(x), dt, channels_last, B, k, P<int32_t>(idx), P<float>(prob), P<float>(logits),
-                             S(stream), use_graph, P<float>(features), l2norm);
+          [=](Engine& e, uintptr_t x, TensorDType dt, bool channels_last, int B, int k, uintptr_t idx, uintptr_t prob,
+              uintptr_t logits, uintptr_t stream, bool use_graph, uintptr_t features, bool l2norm) {
+            e.forward(request(x, B, e.image_size(), e.image_size(), k, idx, prob, logits, features, l2norm, true, dt,
+                              channels_last), S(stream), use_graph);
           },
           py::arg("x"), py::arg("dtype"), py::arg("channels_last"), py::arg("B"), py::arg("k"), py::arg("idx"),
           py::arg("prob"), py::arg("logits"), py::arg("stream"), py::arg("use_graph") = true,
@@ -748,7 +767,9 @@ PYBIND11_MODULE(_C, m) {
              return py::make_tuple(s.fp8, s.scale);
            })
       .def("plan", [=](const Engine& e, int B, int Hin, int Win, int topk, bool tensor_in, bool features) {
-        return plan_list(e.plan_lines(e.plan(B, Hin, Win, topk, tensor_in, features)));
+        // planning reads no buffer: any non-null features pointer asks for the Embed step
+        const PlanSpec spec = e.spec_for(request(0, B, Hin, Win, topk, 0, 0, 0, features ? 1 : 0, false, tensor_in), false);
+        return plan_list(e.plan_lines(e.plan(spec)));
       }, py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("topk") = 1, py::arg("tensor_in") = false,
          py::arg("features") = false)
       .def_property_readonly("feature_dim", &Engine::feature_dim)

@@ -161,14 +161,13 @@ std::vector<PackRegion> Engine::pack_audit(const std::string& arch, const Weight
 }
 
 std::vector<Engine::PlanLine> Engine::plan_audit(const std::string& arch, const WeightMap& weights,
-                                                 const EngineOptions& options, int B, bool native, int num_cus,
-                                                 std::vector<Op>* engine_ops, int num_classes, int image_size,
-                                                 int topk, bool tensor_in, bool features) {
+                                                 const EngineOptions& options, const PlanSpec& spec, int num_cus,
+                                                 std::vector<Op>* engine_ops, int num_classes, int image_size) {
   Engine e(HostOnly{}, arch, weights, num_classes, image_size, options);
   e.num_cus_ = num_cus;
   e.layout_weights();
   if (engine_ops) *engine_ops = e.ops_;
-  return e.plan_lines(e.plan(B, native, options.fork_ds, false, topk, tensor_in, features));
+  return e.plan_lines(e.plan(spec));
 }
 
 // Same graph, packing and calibration as `src`, on another device, with an
@@ -1403,11 +1402,11 @@ struct Engine::Planner {
     steps.push_back(st);
   }
 
-  std::vector<Step> run(bool native, bool side, bool keep_acts, int topk, bool tensor_in, bool features) {
+  std::vector<Step> run(const PlanSpec& spec) {
     // a float tensor takes the resized-input plan: the u8 stems cannot read it
-    if (tensor_in) native = false;
+    const bool tensor_in = spec.tensor_in, native = spec.native && !tensor_in;
     // never a side stream next to a big-tile conv
-    const bool side_ready = side && std::find(path.begin(), path.end(), Path::BigTile) == path.end();
+    const bool side_ready = spec.side && std::find(path.begin(), path.end(), Path::BigTile) == path.end();
     for (size_t oi = 0; oi < ops.size(); oi = steps.back().first_op + steps.back().n_ops) {
       const Op& op = ops[oi];
       switch (op.type) {
@@ -1423,7 +1422,7 @@ struct Engine::Planner {
             emit(tensor_in ? Kernel::PackTensor : Kernel::Preprocess, oi, 1);
           break;
         case OpType::Conv:
-          plan_conv(oi, side_ready, keep_acts);
+          plan_conv(oi, side_ready, spec.keep_acts);
           break;
         case OpType::StemPool: {
           const ConvLayer& L = convs[op.conv];
@@ -1466,21 +1465,38 @@ struct Engine::Planner {
     }
     // top-k: the plan above unchanged (its tail still writes the logits and a
     // top-1 of its own), then the ranking of those logits
-    if (topk > 1) {
-      Step& st = emit(Kernel::SoftmaxTopK, ops.size() - 1, 0);
-      st.count = topk;
-    }
+    if (spec.topk > 1) emit(Kernel::SoftmaxTopK, ops.size() - 1, 0).count = spec.topk;
     // features: the plan above unchanged, then the fc's input as fp32 rows
-    if (features) plan_embed();
+    if (spec.features) plan_embed();
     return std::move(steps);
   }
 };
 
-std::vector<Step> Engine::plan(int B, bool native, bool side, bool keep_acts, int topk, bool tensor_in,
-                               bool features) const {
-  if (topk < 1 || topk > std::min(num_classes_, kMaxTopK))
+void Engine::check_topk(int k) const {
+  if (k < 1 || k > std::min(num_classes_, kMaxTopK))
     throw std::invalid_argument("top-k: k must be in 1..min(num_classes, " + std::to_string(kMaxTopK) + ")");
-  return Planner(*this, B).run(native, side, keep_acts, topk, tensor_in, features);
+}
+
+std::vector<Step> Engine::plan(const PlanSpec& spec) const {
+  check_topk(spec.topk);
+  return Planner(*this, spec.B).run(spec);
+}
+
+PlanSpec Engine::spec_for(const Request& req, bool keep_acts) const {
+  PlanSpec spec;
+  spec.B = req.B;
+  spec.native = req.in.Hin == image_size_ && req.in.Win == image_size_;
+  spec.side = opt_.fork_ds;
+  spec.keep_acts = keep_acts;
+  spec.topk = req.k;
+  spec.tensor_in = req.in.tensor;
+  spec.features = req.features != nullptr;
+  return spec;
+}
+
+Engine::GraphKey Engine::key_of(const Request& req) {
+  return GraphKey{req.in.data, req.B, req.in.Hin, req.in.Win, req.idx, req.prob, req.logits, req.k, req.in.kind(),
+                  req.features, req.features && req.l2norm};
 }
 
 int Engine::feature_dim() const {
@@ -1514,9 +1530,12 @@ std::vector<Engine::PlanLine> Engine::plan_lines(const std::vector<Step>& steps)
 }
 
 // ---------------------------------------------------------------- executor
-void Engine::run_ops(const std::vector<Step>& steps, const Input& in, int B, int32_t* idx, float* prob,
-                     float* logits, hipStream_t s, std::vector<hipEvent_t>* evs, bool trace, float* features,
-                     bool l2norm) {
+void Engine::run_ops(const std::vector<Step>& steps, const Request& req, hipStream_t s, std::vector<hipEvent_t>* evs,
+                     bool trace) {
+  const Input& in = req.in;
+  const int B = req.B;
+  int32_t* const idx = req.idx;
+  float *const prob = req.prob, *const logits = req.logits, *const features = req.features;
   // the u8 kernels and PackTensor each read their own kind of input: a plan
   // made for the other kind is refused before anything is launched
   for (const Step& st : steps) {
@@ -1528,7 +1547,6 @@ void Engine::run_ops(const std::vector<Step>& steps, const Input& in, int B, int
   if (features && (steps.empty() || steps.back().kernel != Kernel::Embed))
     throw std::logic_error("a features buffer needs a plan made with features");
   const uint8_t* const images = in.tensor ? nullptr : (const uint8_t*)in.data;
-  const int Hin = in.Hin, Win = in.Win;
   size_t ei = 0;
   if (evs) DMLC_HIP_CHECK(hipEventRecord((*evs)[ei++], s));
   std::map<int, hipEvent_t> joined;  // activation -> event its side-stream producer recorded
@@ -1576,7 +1594,7 @@ void Engine::run_ops(const std::vector<Step>& steps, const Input& in, int B, int
       case Kernel::Preprocess: {
         const bool paired = op.k == 1;
         const int Wr = paired ? 2 * shapes_[op.out].W : shapes_[op.out].W;
-        preprocess_u8(images, acts_[op.out], B, Hin, Win, image_size_, op.pad, Wr, s, paired);
+        preprocess_u8(images, acts_[op.out], B, in.Hin, in.Win, image_size_, op.pad, Wr, s, paired);
         break;
       }
       case Kernel::PackTensor: {
@@ -1747,9 +1765,9 @@ void Engine::run_ops(const std::vector<Step>& steps, const Input& in, int B, int
         const int src = ops_[st.src_op].out;
         const ActShape& ss = shapes_[src];
         if (st.count > 0)
-          embed_rows(acts_[src], features, B, st.count, ss.C, ss.fp8, ss.scale, l2norm, s);
+          embed_rows(acts_[src], features, B, st.count, ss.C, ss.fp8, ss.scale, req.l2norm, s);
         else
-          embed_rows(acts_[src], features, B, 1, (int)ss.elems_per_image(), false, 1.f, l2norm, s);
+          embed_rows(acts_[src], features, B, 1, (int)ss.elems_per_image(), false, 1.f, req.l2norm, s);
         break;
       }
     }
@@ -1763,43 +1781,18 @@ void Engine::run_ops(const std::vector<Step>& steps, const Input& in, int B, int
 
 void Engine::forward(const uint8_t* images, int B, int Hin, int Win, int32_t* idx, float* prob,
                      float* logits, hipStream_t stream, bool use_graph) {
-  forward_topk(images, B, Hin, Win, 1, idx, prob, logits, stream, use_graph);
+  forward(Request{Input{images, Hin, Win}, B, 1, idx, prob, logits}, stream, use_graph);
 }
 
-void Engine::forward_topk(const uint8_t* images, int B, int Hin, int Win, int k, int32_t* idx, float* prob,
-                          float* logits, hipStream_t stream, bool use_graph, float* features, bool l2norm) {
-  Input in;
-  in.data = images;
-  in.Hin = Hin;
-  in.Win = Win;
-  forward_input(in, B, k, idx, prob, logits, stream, use_graph, features, l2norm);
-}
-
-void Engine::forward_tensor(const void* x, TensorDType dt, bool channels_last, int B, int k, int32_t* idx,
-                            float* prob, float* logits, hipStream_t stream, bool use_graph, float* features,
-                            bool l2norm) {
-  if (dt != TensorDType::F32 && dt != TensorDType::F16 && dt != TensorDType::BF16)
+void Engine::forward(const Request& req, hipStream_t stream, bool use_graph) {
+  if (req.in.tensor && req.in.dt != TensorDType::F32 && req.in.dt != TensorDType::F16 && req.in.dt != TensorDType::BF16)
     throw std::invalid_argument("forward_tensor: unknown dtype");
-  Input in;
-  in.data = x;
-  in.Hin = in.Win = image_size_;
-  in.tensor = true;
-  in.dt = dt;
-  in.channels_last = channels_last;
-  forward_input(in, B, k, idx, prob, logits, stream, use_graph, features, l2norm);
-}
-
-void Engine::forward_input(const Input& in, int B, int k, int32_t* idx, float* prob, float* logits,
-                           hipStream_t stream, bool use_graph, float* features, bool l2norm) {
-  if (B <= 0) return;
-  if (k < 1 || k > std::min(num_classes_, kMaxTopK))
-    throw std::invalid_argument("top-k: k must be in 1..min(num_classes, " + std::to_string(kMaxTopK) + ")");
-  if (k > 1 && (!idx || !prob)) throw std::invalid_argument("top-k: null idx / prob");
-  if (B > max_batch_) throw std::invalid_argument("batch exceeds reserved max_batch");
-  if (!in.data) throw std::invalid_argument("null images");
+  if (req.B <= 0) return;
+  check_topk(req.k);
+  if (req.k > 1 && (!req.idx || !req.prob)) throw std::invalid_argument("top-k: null idx / prob");
+  if (req.B > max_batch_) throw std::invalid_argument("batch exceeds reserved max_batch");
+  if (!req.in.data) throw std::invalid_argument("null images");
   DMLC_HIP_CHECK(hipSetDevice(device_));
-  const int Hin = in.Hin, Win = in.Win;
-  const bool native = Hin == image_size_ && Win == image_size_;
   // Forwards share the activation arena: one on a different stream than the
   // previous forward is ordered after it (an event, only then).
   if (last_stream_valid_ && stream != last_stream_) DMLC_HIP_CHECK(hipStreamWaitEvent(stream, ev_out_, 0));
@@ -1808,15 +1801,14 @@ void Engine::forward_input(const Input& in, int B, int k, int32_t* idx, float* p
     // engine's stream and back (two cross-stream waits cost ~40 us of idle
     // GPU between back-to-back forwards: profiles/r1_graph_gap.txt). The
     // engine's own stream is only used to capture.
-    // (the flag is keyed only next to a buffer: without one it changes nothing)
-    GraphKey key{in.data, B, Hin, Win, idx, prob, logits, k, in.kind(), features, features && l2norm ? 1 : 0};
+    const GraphKey key = key_of(req);
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
-      const std::vector<Step> steps = plan(B, native, opt_.fork_ds, false, k, in.tensor, features != nullptr);
+      const std::vector<Step> steps = plan(spec_for(req, false));
       DMLC_HIP_CHECK(hipStreamSynchronize(stream));
       hipGraph_t g;
       DMLC_HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-      run_ops(steps, in, B, idx, prob, logits, stream_, nullptr, false, features, l2norm);
+      run_ops(steps, req, stream_, nullptr, false);
       DMLC_HIP_CHECK(hipStreamEndCapture(stream_, &g));
       hipGraphExec_t ex;
       DMLC_HIP_CHECK(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
@@ -1827,8 +1819,7 @@ void Engine::forward_input(const Input& in, int B, int k, int32_t* idx, float* p
     DMLC_HIP_CHECK(hipGraphLaunch(it->second, stream));
   } else {  // eager launches straight onto the caller's stream
     DMLC_TRACE("engine.forward");
-    run_ops(plan(B, native, opt_.fork_ds, true, k, in.tensor, features != nullptr), in, B, idx, prob, logits, stream,
-            nullptr, true, features, l2norm);
+    run_ops(plan(spec_for(req, true)), req, stream, nullptr, true);
   }
   DMLC_HIP_CHECK(hipEventRecord(ev_out_, stream));
   last_stream_ = stream;
@@ -1843,12 +1834,10 @@ std::vector<std::pair<std::string, float>> Engine::profile(const uint8_t* images
   std::vector<hipEvent_t> evs(ops_.size() + 1);
   for (auto& e : evs) DMLC_HIP_CHECK(hipEventCreate(&e));
   // per-op event timing keeps every op on one stream
-  Input in;
-  in.data = images;
-  in.Hin = Hin;
-  in.Win = Win;
-  run_ops(plan(B, Hin == image_size_ && Win == image_size_, false, true), in, B, nullptr, nullptr, nullptr, stream_, &evs,
-          true);
+  const Request req{Input{images, Hin, Win}, B};
+  PlanSpec spec = spec_for(req, true);
+  spec.side = false;
+  run_ops(plan(spec), req, stream_, &evs, true);
   DMLC_HIP_CHECK(hipStreamSynchronize(stream_));
   std::vector<std::pair<std::string, float>> out;
   for (size_t i = 0; i < ops_.size(); ++i) {

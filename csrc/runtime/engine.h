@@ -200,6 +200,29 @@ struct Step {
   int src_op = -1;       // Embed: the op whose output activation it reads
 };
 
+// What a plan depends on (Engine::plan): the top-1 u8 plan, with steps swapped or appended by the last three fields.
+struct PlanSpec {
+  int B = 0;
+  bool native = false;  // the images already have the model's size
+  // downsample convs may go to the side stream (fork_ds; dropped when the plan has a big-tile conv, whose
+  // split-K slices spin on each other and need their CUs)
+  bool side = false;
+  // every activation a test may read is stored (eager / profile runs; a graph capture drops the last conv's
+  // when its pool is fused)
+  bool keep_acts = false;
+  // > 1: then one SoftmaxTopK step on the logits the tail wrote; it belongs to the last op and covers none
+  // (n_ops 0). 1 <= topk <= min(num_classes, kMaxTopK), or plan() throws std::invalid_argument
+  int topk = 1;
+  // a float tensor input: the native = false plan step for step, with PackTensor in place of Preprocess (the u8
+  // stems never run; `native` is not looked at)
+  bool tensor_in = false;
+  // then one Embed step (after SoftmaxTopK when there is one; last op, n_ops 0) that writes the fc's input F as
+  // fp32 rows. Where a step of the plan stores F (an AvgPoolGlobal step, a conv epilogue's pool_op, AlexNet's
+  // classifier.4) it reads F; where HeadFused covers the pool, F is never written, and it averages the pool's
+  // input (always stored then) exactly as the pool would.
+  bool features = false;
+};
+
 class Engine {
  public:
   // arch: resnet18 | resnet34 | resnet50 | alexnet | resnet50_fp8 (layers 2-4
@@ -224,45 +247,21 @@ class Engine {
   static std::vector<PackRegion> pack_audit(const std::string& arch, const WeightMap& weights,
                                             const EngineOptions& options, size_t* total,
                                             int num_classes = 1000, int image_size = 224);
-  // The launches of one forward of B images. native: the images already have
-  // the model's size; side: downsample convs may go to the side stream
-  // (fork_ds; dropped when the plan has a big-tile conv, whose split-K slices
-  // spin on each other and need their CUs); keep_acts: every activation a
-  // test may read is stored (eager / profile runs; a graph capture drops the
-  // last conv's when its pool is fused). Host integer logic only.
-  // topk > 1 (forward_topk): the same steps, then one SoftmaxTopK step on the
-  // logits the tail wrote; it belongs to the last op and covers none (n_ops 0).
-  // tensor_in (forward_tensor): the native = false plan step for step, with
-  // PackTensor in place of Preprocess (the u8 stems never run; `native` is
-  // not looked at).
-  // features (a forward with a features buffer): the same steps, then one
-  // Embed step (after SoftmaxTopK when there is one; last op, n_ops 0) that
-  // writes the fc's input F as fp32 rows. Where a step of the plan stores F
-  // (an AvgPoolGlobal step, a conv epilogue's pool_op, AlexNet's classifier.4)
-  // it reads F; where HeadFused covers the pool, F is never written, and it
-  // averages the pool's input (always stored then) exactly as the pool would.
-  std::vector<Step> plan(int B, bool native, bool side, bool keep_acts, int topk = 1, bool tensor_in = false,
-                         bool features = false) const;
-  // The plan a graph-captured forward(B, Hin, Win) / forward_topk(.., topk) /
-  // forward_tensor (tensor_in) runs.
-  std::vector<Step> plan(int B, int Hin, int Win, int topk = 1, bool tensor_in = false, bool features = false) const {
-    return plan(B, Hin == image_size_ && Win == image_size_, opt_.fork_ds, false, topk, tensor_in, features);
-  }
+  // The launches of one forward. Host integer logic only.
+  std::vector<Step> plan(const PlanSpec& spec) const;
   // A step's extra fields as text, e.g. "ds=layer2.0.downsample.0 wreg".
   std::string step_detail(const Step& st) const;
   // Host-only like pack_audit (the layout pass runs first: the plan reads
-  // wf_off, cat_off, npad): the plan of a graph-captured native / resized
-  // forward on a device with num_cus compute units, as text. *engine_ops = the
-  // graph's ops.
+  // wf_off, cat_off, npad): plan(spec) on a device with num_cus compute units,
+  // as text. *engine_ops = the graph's ops.
   struct PlanLine {
     std::string kernel, first_op, detail;
     int n_ops = 1;
   };
   static std::vector<PlanLine> plan_audit(const std::string& arch, const WeightMap& weights,
-                                          const EngineOptions& options, int B, bool native, int num_cus,
+                                          const EngineOptions& options, const PlanSpec& spec, int num_cus,
                                           std::vector<Op>* engine_ops = nullptr, int num_classes = 1000,
-                                          int image_size = 224, int topk = 1, bool tensor_in = false,
-                                          bool features = false);
+                                          int image_size = 224);
   std::vector<PlanLine> plan_lines(const std::vector<Step>& steps) const;
   void* weight_arena() const { return warena_; }
 
@@ -282,34 +281,53 @@ class Engine {
   // Allocate the activation arena for batches up to max_batch.
   void reserve(int max_batch);
 
-  // images: device u8 [B, Hin, Win, 3]. Outputs (device): idx int32 [B],
-  // prob f32 [B], optional logits f32 [B, num_classes].
-  // Ordered after all prior work on `stream`; later work on `stream` sees
-  // the outputs. use_graph: replay a captured hipGraph for this exact
-  // (B, pointers) signature (captured on first use).
+  // What a forward reads (device memory): u8 [B, Hin, Win, 3] images, or a float tensor the caller has already
+  // normalised, [B, 3, S, S] contiguous or channels_last [B, S, S, 3], Hin = Win = S = image_size(), of dtype dt
+  // (pack_tensor's contract: the values are used as given).
+  struct Input {
+    const void* data = nullptr;
+    int Hin = 0, Win = 0;
+    bool tensor = false;
+    TensorDType dt = TensorDType::F32;
+    bool channels_last = false;
+    int kind() const { return tensor ? 1 + 2 * (int)dt + (channels_last ? 1 : 0) : 0; }  // 0: u8
+  };
+  // One forward: what it reads and the device buffers it writes.
+  struct Request {
+    Input in;
+    int B = 0;
+    // the k best classes per image in descending order (softmax_topk's contract), ranked by one more kernel if k > 1
+    int k = 1;
+    int32_t* idx = nullptr;   // [B, k]; may be null when k = 1
+    float* prob = nullptr;    // [B, k]; may be null when k = 1
+    float* logits = nullptr;  // [B, num_classes], or null
+    // [B, feature_dim()], or null: the vector the last fc reads (the pooled feature; AlexNet's classifier.4 output),
+    // widened from the bf16 the fc multiplies. One more launch after the forward's own, which are unchanged.
+    float* features = nullptr;
+    bool l2norm = false;  // each features row scaled to unit L2 norm (embed_rows)
+  };
+  // What tells one captured graph from another: every pointer and size of the request, and the
+  // input kind, so a u8 and a tensor forward, or two dtypes, on one pointer never replay each other's.
+  struct GraphKey {
+    const void* data;
+    int B, Hin, Win;
+    const void *idx, *prob, *logits;
+    int k, input_kind;
+    const void* features;
+    bool l2norm;  // false without a features buffer: the flag changes nothing then
+    auto tie() const { return std::tie(data, B, Hin, Win, idx, prob, logits, k, input_kind, features, l2norm); }
+    bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
+  };
+  static GraphKey key_of(const Request& req);  // host only
+  // The plan of req's forward here; keep_acts is false under a graph capture.
+  PlanSpec spec_for(const Request& req, bool keep_acts) const;
+
+  // Ordered after all prior work on `stream`; later work on `stream` sees the outputs. use_graph: replay the
+  // hipGraph captured (on first use) for key_of(req). B <= 0 does nothing; std::invalid_argument on a bad request.
+  void forward(const Request& req, hipStream_t stream, bool use_graph);
+  // The top-1 forward of u8 images (the shape of the reference's query).
   void forward(const uint8_t* images, int B, int Hin, int Win, int32_t* idx, float* prob,
                float* logits, hipStream_t stream, bool use_graph);
-  // The same forward with the k best classes per image: idx int32 [B, k] and
-  // prob f32 [B, k] in descending order (softmax_topk's contract), 1 <= k <=
-  // min(num_classes, kMaxTopK). k = 1 is forward(); for k > 1 the tail's own
-  // top-1 goes to engine scratch and one more kernel ranks the logits.
-  // features: device fp32 [B, feature_dim()], or null. The vector the last fc
-  // reads (the pooled feature; AlexNet's classifier.4 output), widened from
-  // the bf16 the fc multiplies; l2norm: each row scaled to unit L2 norm
-  // (embed_rows). One more launch after the forward's own, which are
-  // unchanged. Graphs are keyed by the pointer and the flag as well.
-  void forward_topk(const uint8_t* images, int B, int Hin, int Win, int k, int32_t* idx, float* prob,
-                    float* logits, hipStream_t stream, bool use_graph, float* features = nullptr,
-                    bool l2norm = false);
-  // The same forward on a float tensor the caller has already normalised:
-  // x is device [B, 3, S, S] contiguous, or [B, S, S, 3] contiguous with
-  // channels_last, S = image_size(), of dtype dt (pack_tensor's contract: the
-  // values are used as given). k = 1: forward()'s outputs; k > 1:
-  // forward_topk()'s. Graphs are keyed by the input kind as well, so a u8 and
-  // a tensor forward, or two dtypes, on one pointer never replay each other's.
-  void forward_tensor(const void* x, TensorDType dt, bool channels_last, int B, int k, int32_t* idx, float* prob,
-                      float* logits, hipStream_t stream, bool use_graph, float* features = nullptr,
-                      bool l2norm = false);
 
   // Eager forward with an event pair around every op: (op name, ms).
   std::vector<std::pair<std::string, float>> profile(const uint8_t* images, int B, int Hin,
@@ -339,25 +357,12 @@ class Engine {
   void init_device();
   void mark_fp8();
   void calibrate(const WeightMap& w);
-  // Launch the steps of plan(B, native, ...) in order. evs: an event after
-  // every op (profile); trace: a host trace range per launching op. In a plan
-  // that ends with SoftmaxTopK, idx / prob are that step's [B, k] outputs.
-  // What a forward reads: u8 [B, Hin, Win, 3] images, or a float tensor
-  // [B, 3, S, S] / channels_last [B, S, S, 3] (Hin = Win = image_size_).
-  struct Input {
-    const void* data = nullptr;
-    int Hin = 0, Win = 0;
-    bool tensor = false;
-    TensorDType dt = TensorDType::F32;
-    bool channels_last = false;
-    int kind() const { return tensor ? 1 + 2 * (int)dt + (channels_last ? 1 : 0) : 0; }  // graph key
-  };
-  // A plan that ends with Embed writes features (normalised: l2norm).
-  void run_ops(const std::vector<Step>& steps, const Input& in, int B, int32_t* idx, float* prob, float* logits,
-               hipStream_t s, std::vector<hipEvent_t>* evs, bool trace, float* features = nullptr,
-               bool l2norm = false);
-  void forward_input(const Input& in, int B, int k, int32_t* idx, float* prob, float* logits, hipStream_t stream,
-                     bool use_graph, float* features, bool l2norm);
+  // Launch the steps of plan(spec_for(req, ..)) in order. evs: an event after every op (profile); trace: a host
+  // trace range per launching op. A plan made for another kind of input, or with / without features where the
+  // request differs, is refused before anything is launched.
+  void run_ops(const std::vector<Step>& steps, const Request& req, hipStream_t s, std::vector<hipEvent_t>* evs,
+               bool trace);
+  void check_topk(int k) const;  // std::invalid_argument outside 1..min(num_classes, kMaxTopK)
   // A conv op's launch arguments in two parts: the geometry (shapes, padding,
   // flags, scales, tile, split-K, persistent grid), which is all the planner
   // and the kernels' *_supported checks see, and the operands (x, w, bias,
@@ -395,15 +400,12 @@ class Engine {
   void* head_ws_ = nullptr;  // fused head partials + per-group tickets
   size_t head_ws_bytes_ = 0;
 
-
   hipStream_t stream_ = nullptr;
   hipEvent_t ev_out_ = nullptr;  // end of the last forward (on last_stream_)
   hipStream_t last_stream_ = nullptr;  // stream of the last direct graph replay (ev_out_ marks its end)
   bool last_stream_valid_ = false;
   hipStream_t side_ = nullptr;                      // downsample branch
   std::vector<hipEvent_t> fork_evs_, join_evs_;     // per op
-  // ..., logits, k, Input::kind, features, l2norm
-  using GraphKey = std::tuple<const void*, int, int, int, void*, void*, void*, int, int, void*, int>;
   std::map<GraphKey, hipGraphExec_t> graphs_;
 };
 

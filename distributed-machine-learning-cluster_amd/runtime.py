@@ -173,14 +173,10 @@ class InferenceEngine:
         if src[0] == "tensor":
             _, ptr, dt, channels_last = src
             self._e.forward_tensor(ptr, dt, channels_last, B, topk, idx.data_ptr(), prob.data_ptr(), lp, stream,
-                                   use_graph, features=fp, l2norm=l2norm)
-        elif topk == 1 and features is None:
+                                   use_graph, fp, l2norm)
+        else:  # positionally: keyword arguments cost a batch-1 query most of a microsecond in the binding
             _, ptr, H, W = src
-            self._e.forward(ptr, B, H, W, idx.data_ptr(), prob.data_ptr(), lp, stream, use_graph)
-        else:
-            _, ptr, H, W = src
-            self._e.forward_topk(ptr, B, H, W, topk, idx.data_ptr(), prob.data_ptr(), lp, stream, use_graph,
-                                 features=fp, l2norm=l2norm)
+            self._e.forward_topk(ptr, B, H, W, topk, idx.data_ptr(), prob.data_ptr(), lp, stream, use_graph, fp, l2norm)
         return tuple(t for t in (idx, prob, logits, features) if t is not None)
 
     def profile(self, images: torch.Tensor) -> list[tuple[str, float]]:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Measurements for the embeddings path (csrc/kernels/embed.hip and the
-features buffer of Engine::forward_topk), written as plain text. One GPU.
+features buffer of Engine.forward_topk), written as plain text. One GPU.
 
   kernel  embed_rows at B=256 for (HW, C) = (1, 512), (1, 2048), (1, 4096),
           (49, 512) bf16 and (49, 2048) e4m3, plain and normalised: device

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Measurements for float-tensor input (csrc/kernels/pack_tensor.hip and
-Engine::forward_tensor), written as plain text. One GPU.
+Engine.forward_tensor), written as plain text. One GPU.
 
   kernel  pack_tensor alone at B=256, S=224 into the fused ResNet stem's paired
           image (pad 3) for fp32 NCHW, bf16 NCHW and fp32 channels_last, next

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Measurements for softmax + top-k (csrc/kernels/softmax_topk.hip and
-Engine::forward_topk), written as plain text. One GPU.
+Engine.forward_topk), written as plain text. One GPU.
 
   kernel  ops.softmax_topk at B=256, N=1000 for k = 1, 5, 16 next to
           ops.softmax_top1 on the same logits: device events around blocks of
