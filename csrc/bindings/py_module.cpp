@@ -477,12 +477,21 @@ PYBIND11_MODULE(_C, m) {
   m.def("sim_topk_ws_bytes", &sim_topk_ws_bytes, py::arg("B"), py::arg("k"), py::arg("slices"));
   m.def("sim_topk", [](uintptr_t q, TensorDType qdt, uintptr_t q_scale, uintptr_t g, uintptr_t g_scale, int B, long N,
                        int D, int k, uintptr_t idx, uintptr_t score, uintptr_t ws, size_t ws_bytes, int num_cus,
-                       uintptr_t stream, int slices) {
+                       uintptr_t stream, int slices, uintptr_t g_label, uintptr_t q_want) {
     sim_topk(P<void>(q), qdt, P<float>(q_scale), P<void>(g), P<float>(g_scale), B, N, D, k, P<int32_t>(idx),
-             P<float>(score), P<void>(ws), ws_bytes, num_cus, S(stream), slices);
+             P<float>(score), P<void>(ws), ws_bytes, num_cus, S(stream), slices, P<int32_t>(g_label),
+             P<int32_t>(q_want));
   }, py::arg("q"), py::arg("dtype"), py::arg("q_scale"), py::arg("g"), py::arg("g_scale"), py::arg("B"), py::arg("N"),
         py::arg("D"), py::arg("k"), py::arg("idx"), py::arg("score"), py::arg("ws"), py::arg("ws_bytes"),
-        py::arg("num_cus"), py::arg("stream"), py::arg("slices") = 0, py::call_guard<py::gil_scoped_release>());
+        py::arg("num_cus"), py::arg("stream"), py::arg("slices") = 0, py::arg("g_label") = 0, py::arg("q_want") = 0,
+        py::call_guard<py::gil_scoped_release>());
+  m.def("knn_vote", [](uintptr_t idx, uintptr_t score, uintptr_t g_label, long N, int B, int k, bool weighted,
+                       uintptr_t label, uintptr_t share, uintptr_t stream) {
+    knn_vote(P<int32_t>(idx), P<float>(score), P<int32_t>(g_label), N, B, k, weighted, P<int32_t>(label),
+             P<float>(share), S(stream));
+  }, py::arg("idx"), py::arg("score"), py::arg("g_label"), py::arg("N"), py::arg("B"), py::arg("k"),
+        py::arg("weighted"), py::arg("label"), py::arg("share"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
   m.def("gallery_pack", [](uintptr_t rows, uintptr_t g, uintptr_t inv_norm, int M, int D, uintptr_t stream) {
     gallery_pack(P<float>(rows), P<void>(g), P<float>(inv_norm), M, D, S(stream));
   }, py::arg("rows"), py::arg("g"), py::arg("inv_norm"), py::arg("M"), py::arg("D"), py::arg("stream"),
@@ -501,14 +510,35 @@ PYBIND11_MODULE(_C, m) {
       .def_property_readonly("max_batch", &Gallery::max_batch)
       .def_property_readonly("size", &Gallery::size)
       .def_property_readonly("metric", [](const Gallery& g) { return std::string(g.cosine() ? "cosine" : "dot"); })
-      .def("add", [](Gallery& g, uintptr_t rows, int M, uintptr_t stream) { return g.add(P<float>(rows), M, S(stream)); },
-           py::arg("rows"), py::arg("M"), py::arg("stream"), py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("live", &Gallery::live)
+      .def("add",
+           [](Gallery& g, uintptr_t rows, int M, uintptr_t stream, uintptr_t labels) {
+             return g.add(P<float>(rows), M, P<int32_t>(labels), S(stream));
+           },
+           py::arg("rows"), py::arg("M"), py::arg("stream"), py::arg("labels") = 0,
+           py::call_guard<py::gil_scoped_release>())
+      .def("remove",
+           [](Gallery& g, const std::vector<long>& ids, uintptr_t stream) {
+             g.remove(ids.data(), (long)ids.size(), S(stream));
+           },
+           py::arg("ids"), py::arg("stream"), py::call_guard<py::gil_scoped_release>())
       .def("search",
-           [](Gallery& g, uintptr_t q, TensorDType qdt, int B, int k, uintptr_t idx, uintptr_t score, uintptr_t stream) {
-             g.search(P<void>(q), qdt, B, k, P<int32_t>(idx), P<float>(score), S(stream));
+           [](Gallery& g, uintptr_t q, TensorDType qdt, int B, int k, uintptr_t idx, uintptr_t score, uintptr_t stream,
+              uintptr_t q_want) {
+             g.search(P<void>(q), qdt, B, k, P<int32_t>(idx), P<float>(score), S(stream), P<int32_t>(q_want));
            },
            py::arg("q"), py::arg("dtype"), py::arg("B"), py::arg("k"), py::arg("idx"), py::arg("score"),
-           py::arg("stream"), py::call_guard<py::gil_scoped_release>())
+           py::arg("stream"), py::arg("q_want") = 0, py::call_guard<py::gil_scoped_release>())
+      .def("classify",
+           [](Gallery& g, uintptr_t q, TensorDType qdt, int B, int k, bool weighted, uintptr_t label, uintptr_t share,
+              uintptr_t stream) {
+             g.classify(P<void>(q), qdt, B, k, weighted, P<int32_t>(label), P<float>(share), S(stream));
+           },
+           py::arg("q"), py::arg("dtype"), py::arg("B"), py::arg("k"), py::arg("weighted"), py::arg("label"),
+           py::arg("share"), py::arg("stream"), py::call_guard<py::gil_scoped_release>())
+      .def("read_labels",
+           [](Gallery& g, uintptr_t dst, uintptr_t stream) { g.read_labels(P<int32_t>(dst), S(stream)); },
+           py::arg("dst"), py::arg("stream"), py::call_guard<py::gil_scoped_release>())
       .def("clear", &Gallery::clear);
 
   // ---------------------------------------------------------------- jpeg

@@ -473,6 +473,15 @@ void embed_rows(const void* x, float* out, int B, int HW, int C, bool in_fp8, fl
 // workgroup per CU, at most sim_topk_max_slices), merged by a second kernel
 // when there is more than one; blocks of 256 queries are separate launches.
 // ws: sim_topk_ws_bytes(B, k, slices) bytes, no initial contents needed.
+//
+// The row filter (another instantiation of the kernel; without g_label the
+// launches and the bits are those of the unfiltered search). g_label: int32
+// [N]; row n is a candidate only if g_label[n] >= 0 (a negative label marks a
+// removed row). q_want: int32 [B], only together with g_label: query b
+// accepts only rows with g_label[n] == q_want[b] if q_want[b] >= 0, any live
+// row otherwise (or when q_want is null). A row that fails the filter wins no
+// rank whatever its score. A query with fewer than k candidates gets
+// idx = -1, score = -inf at the ranks without one, after all real ranks.
 bool sim_topk_supported(int D);  // D % 32 == 0, 32 <= D <= 4096
 int sim_topk_slices(int B, long N, int num_cus);
 int sim_topk_max_slices(long N);  // min(tiles, 512)
@@ -482,7 +491,25 @@ size_t sim_topk_ws_bytes(int B, int k, int slices);
 void sim_topk(const void* q, TensorDType qdt /*F32 or BF16*/, const float* q_scale /*[B] or null*/,
               const void* g /*bf16 [N, D]*/, const float* g_scale /*[N] or null*/, int B, long N, int D, int k,
               int32_t* idx /*[B,k]*/, float* score /*[B,k]*/, void* ws, size_t ws_bytes, int num_cus, hipStream_t s,
-              int slices_override = 0);
+              int slices_override = 0, const int32_t* g_label /*[N] or null*/ = nullptr,
+              const int32_t* q_want /*[B] or null*/ = nullptr);
+// labels[ids[i]] = -1 for i < M: marks gallery rows removed. ids in 0..N-1
+// (the caller checks them; an id outside is skipped).
+void gallery_unlabel(int32_t* labels, const int32_t* ids, int M, long N, hipStream_t s);
+
+// k-NN vote (knn_vote.hip) over a search's answer idx / score [B, k] and the
+// gallery's labels g_label [N]: per query the winning label and its share of
+// the vote. Rank j votes iff 0 <= idx[b][j] < N, with label
+// g_label[idx[b][j]] and weight 1 (uniform) or max(score[b][j], 0)
+// (weighted). A label's total is the fp32 sum of its ranks' weights in
+// ascending rank order from 0; the largest total wins, among equal totals the
+// label whose best (lowest) rank comes first. share = the winner's total /
+// the fp32 sum of all voting weights in ascending rank order (IEEE divide; 0
+// if that sum is 0). No voter: label -1, share 0. 1 <= k <= kMaxTopK. One
+// launch, no allocation, no synchronisation.
+void knn_vote(const int32_t* idx, const float* score, const int32_t* g_label, long N, int B, int k, bool weighted,
+              int32_t* label /*[B]*/, float* share /*[B]*/, hipStream_t s);
+
 // fp32 rows [M, D] -> bf16 (nearest even) g [M, D]; inv_norm (or null): [M],
 // 1 / max(sqrt(sum v^2), 1e-12) of the rounded values v, summed in fp32:
 // embed_rows' normalisation rule on what the MFMA reads. D % 8 == 0,

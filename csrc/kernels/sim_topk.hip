@@ -52,6 +52,16 @@
 // winner's lane advances that head. The comparisons are the same total order
 // on (score, n), so the answer is bit-identical for every slice count.
 //
+// The row filter (FILTER): g_label[n] < 0 marks a removed row, and a query
+// with want >= 0 accepts only rows labelled want. A tile's 128 labels ride
+// with its first stage as the scales do; after the scaling step a score whose
+// row fails its query's filter becomes -inf, exactly what a row past N is, so
+// the threshold, ballot and insertion logic never see it (-inf > thr is false
+// even for thr = -inf). A query with fewer than k candidates keeps empty
+// slots (-inf, INT_MAX) at the end of its list; whatever writes the answer
+// (this kernel at one slice, else the merge) turns their INT_MAX into -1.
+// The FILTER = false instantiations are the unfiltered kernels unchanged.
+//
 // gallery_pack: fp32 rows -> bf16 (nearest even), optionally with
 // 1 / max(sqrt(sum v^2), 1e-12) of the rounded values v (fp32 squares summed
 // per lane and across the wave; IEEE root and divide): embed.hip's
@@ -66,6 +76,8 @@ namespace dmlc {
 
 namespace {
 
+typedef int intx4 __attribute__((ext_vector_type(4)));
+
 constexpr int kBQ = 256;  // queries per workgroup
 constexpr int kBG = 128;  // gallery rows per tile
 constexpr int kKB = 64;   // K block per stage
@@ -76,7 +88,9 @@ constexpr int kSlots = 2;
 constexpr int kListS = kSlots * kStage;              // float [kBQ][kMaxTopK]
 constexpr int kListI = kListS + kBQ * kMaxTopK * 4;  // int   [kBQ][kMaxTopK]
 constexpr int kGScale = kListI + kBQ * kMaxTopK * 4;  // float [2][kBG]
-constexpr int kLds = kGScale + 2 * kBG * 4;
+constexpr int kGLabel = kGScale + 2 * kBG * 4;  // int   [2][kBG] (FILTER)
+constexpr int kLdsPlain = kGLabel;               // what the unfiltered kernel is launched with
+constexpr int kLds = kGLabel + 2 * kBG * 4;
 constexpr int kMaxSlices = 512;  // 8 heads a lane in the merge
 constexpr int kMaxD = 4096;
 static_assert(kLds <= 160 * 1024, "LDS per CU");
@@ -108,17 +122,21 @@ __device__ __forceinline__ void list_insert(float* ls, int* li, int k, float s, 
 
 // q: bf16 [Bq, D], this block's queries; g: bf16 [N, D]. Slice blockIdx.x of
 // gridDim.x takes tiles [t0, t1). out_s / out_i: [Bq][gridDim.x][k].
-template <bool SCALED>
+// FILTER: g_label [N] (never null), q_want [Bq] or null.
+template <bool SCALED, bool FILTER>
 __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const bf16* __restrict__ q, const float* __restrict__ q_scale,
                                                           const bf16* __restrict__ g,
                                                           const float* __restrict__ g_scale, int Bq, long N, int D,
                                                           int k, float* __restrict__ out_s,
-                                                          int32_t* __restrict__ out_i) {
+                                                          int32_t* __restrict__ out_i,
+                                                          const int32_t* __restrict__ g_label,
+                                                          const int32_t* __restrict__ q_want) {
   extern __shared__ __attribute__((aligned(16))) uint4 smem[];
   char* lds = (char*)smem;
   float* ls = (float*)(lds + kListS);
   int* li = (int*)(lds + kListI);
   float* gsl = (float*)(lds + kGScale);
+  int* gll = (int*)(lds + kGLabel);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fq = lane >> 4;
@@ -137,11 +155,13 @@ __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const bf16* __restrict
   }
   if (SCALED && !g_scale && tid < 2 * kBG) gsl[tid] = 1.f;
   float thr[2], qs[2];
+  int want[2];  // (FILTER) >= 0: the only label the query accepts
 #pragma unroll
   for (int qf = 0; qf < 2; ++qf) {
     const int b = 32 * wave + 16 * qf + fr;
     thr[qf] = b < Bq ? -INFINITY : INFINITY;  // a query past B never has a candidate
     qs[qf] = SCALED && q_scale && b < Bq ? q_scale[b] : 1.f;
+    want[qf] = FILTER && q_want && b < Bq ? q_want[b] : -1;
   }
   lgkm_wait();
 
@@ -177,6 +197,10 @@ __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const bf16* __restrict
       const long n = n0 + 64 * wave + lane;
       dma4(g_scale + (n < N ? n : N - 1), gsl + (tile & 1) * kBG + 64 * wave);
     }
+    if (FILTER && kb == 0 && wave < 2) {
+      const long n = n0 + 64 * wave + lane;
+      dma4(g_label + (n < N ? n : N - 1), gll + (tile & 1) * kBG + 64 * wave);
+    }
   };
 
   floatx4 acc[8][2];
@@ -190,7 +214,7 @@ __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const bf16* __restrict
   for (int t = 0; t < nt;) {
     // this wave's DMA of this stage has landed, after the barrier everyone's
     // has, and every wave is done with the previous stage, whose slot (and,
-    // at a tile's first block, whose tile's scale buffer) the next DMA reuses
+    // at a tile's first block, whose tile's scale and label buffers) the next DMA reuses
     vm_wait<0>();
     __builtin_amdgcn_s_barrier();
     if (kb + 1 < nk) dma_stage(t0 + t, kb + 1, slot ^ 1);
@@ -230,6 +254,18 @@ __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const bf16* __restrict
           for (int qf = 0; qf < 2; ++qf)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[gf][qf][r] = (acc[gf][qf][r] * qs[qf]) * sc[r];
+        }
+      }
+      if constexpr (FILTER) {  // a row that fails the query's filter is no candidate
+        const int* gl = gll + ((t0 + t) & 1) * kBG;
+#pragma unroll
+        for (int gf = 0; gf < 8; ++gf) {
+          const intx4 lb = *(const intx4*)(gl + 16 * gf + 4 * fq);
+#pragma unroll
+          for (int qf = 0; qf < 2; ++qf)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (lb[r] < 0 || (want[qf] >= 0 && lb[r] != want[qf])) acc[gf][qf][r] = -INFINITY;
         }
       }
       if (n0 + kBG > N) {  // (uniform) a partial tile: rows past N are no candidates
@@ -293,7 +329,8 @@ __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const bf16* __restrict
       if (b < Bq) {
         const long o = ((long)b * slices + slice) * k + j;
         out_s[o] = ls[b * kMaxTopK + j];
-        out_i[o] = li[b * kMaxTopK + j];
+        const int n = li[b * kMaxTopK + j];
+        out_i[o] = FILTER && slices == 1 && n == INT_MAX ? -1 : n;  // (an empty rank of the answer itself)
       }
     }
   }
@@ -312,7 +349,9 @@ __device__ __forceinline__ void wave_argmax(float& best, int& bi) {
   }
 }
 
-// cs / ci: [B][slices][k], every slice's list sorted; one wave per query
+// cs / ci: [B][slices][k], every slice's list sorted; one wave per query.
+// FILTER: lists may end in empty slots (-inf, INT_MAX), written as idx -1.
+template <bool FILTER>
 __global__ __launch_bounds__(256) void sim_merge_kernel(const float* __restrict__ cs, const int32_t* __restrict__ ci,
                                                         int B, int slices, int k, int32_t* __restrict__ idx,
                                                         float* __restrict__ score) {
@@ -347,7 +386,10 @@ __global__ __launch_bounds__(256) void sim_merge_kernel(const float* __restrict_
       my_i = bi;
       my_v = best;
     }
-    // rows are distinct across slices, so one head at most is the winner
+    // rows are distinct across slices, so one head at most is the winner,
+    // unless (FILTER) the winner is the empty slot (-inf, INT_MAX): then every
+    // head is empty, all of them advance, and as the lists are sorted what
+    // follows an empty slot is empty too, so nothing is skipped
 #pragma unroll
     for (int j = 0; j < H; ++j) {
       const int sl = lane + 64 * j;
@@ -359,7 +401,7 @@ __global__ __launch_bounds__(256) void sim_merge_kernel(const float* __restrict_
     }
   }
   if (lane < k) {
-    idx[(long)b * k + lane] = my_i;
+    idx[(long)b * k + lane] = FILTER && my_i == INT_MAX ? -1 : my_i;
     score[(long)b * k + lane] = my_v;
   }
 }
@@ -391,6 +433,15 @@ __global__ __launch_bounds__(256) void gallery_pack_kernel(const void* __restric
     ss = wave_sum(ss);
     if (lane == 0) inv_norm[m] = 1.f / fmaxf(sqrtf(ss), 1e-12f);
   }
+}
+
+// labels[ids[i]] = -1: a removed row (equal ids write the same value)
+__global__ __launch_bounds__(256) void gallery_unlabel_kernel(int32_t* __restrict__ labels,
+                                                              const int32_t* __restrict__ ids, int M, long N) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= M) return;
+  const int n = ids[i];
+  if (n >= 0 && n < N) labels[n] = -1;
 }
 
 long sim_tiles(long N) { return (N + kBG - 1) / kBG; }
@@ -435,6 +486,14 @@ void gallery_pack(const float* rows, void* g, float* inv_norm, int M, int D, hip
   DMLC_HIP_CHECK(hipGetLastError());
 }
 
+void gallery_unlabel(int32_t* labels, const int32_t* ids, int M, long N, hipStream_t s) {
+  if (M < 0 || N < 0) throw std::invalid_argument("gallery_unlabel: negative size");
+  if (M == 0) return;
+  if (!labels || !ids) throw std::invalid_argument("gallery_unlabel: null labels or ids");
+  hipLaunchKernelGGL(gallery_unlabel_kernel, dim3((M + 255) / 256), dim3(256), 0, s, labels, ids, M, N);
+  DMLC_HIP_CHECK(hipGetLastError());
+}
+
 void gallery_inv_norms(const void* rows_bf16, float* inv_norm, int M, int D, hipStream_t s) {
   if (D < 8 || D % 8 || D > 8192) throw std::invalid_argument("gallery_inv_norms: needs D % 8 == 0, 8 <= D <= 8192");
   if (M < 0) throw std::invalid_argument("gallery_inv_norms: M < 0");
@@ -448,12 +507,13 @@ void gallery_inv_norms(const void* rows_bf16, float* inv_norm, int M, int D, hip
 
 void sim_topk(const void* q, TensorDType qdt, const float* q_scale, const void* g, const float* g_scale, int B, long N,
               int D, int k, int32_t* idx, float* score, void* ws, size_t ws_bytes, int num_cus, hipStream_t s,
-              int slices_override) {
+              int slices_override, const int32_t* g_label, const int32_t* q_want) {
   if (!sim_topk_supported(D)) throw std::invalid_argument("sim_topk: needs D % 32 == 0, 32 <= D <= 4096");
   if (qdt != TensorDType::F32 && qdt != TensorDType::BF16) throw std::invalid_argument("sim_topk: queries are fp32 or bf16");
   if (B < 0) throw std::invalid_argument("sim_topk: B < 0");
   if (N < 1 || N > INT_MAX) throw std::invalid_argument("sim_topk: N outside 1..2^31 - 1");
   if (k < 1 || k > N || k > kMaxTopK) throw std::invalid_argument("sim_topk: k must be in 1..min(N, kMaxTopK)");
+  if (q_want && !g_label) throw std::invalid_argument("sim_topk: q_want needs g_label");
   if (B == 0) return;
   if (!q || !g || !idx || !score || !ws || (((uintptr_t)q | (uintptr_t)g | (uintptr_t)ws) & 15))
     throw std::invalid_argument("sim_topk: null / misaligned operand (q, g and ws need 16 B)");
@@ -477,17 +537,27 @@ void sim_topk(const void* q, TensorDType qdt, const float* q_scale, const void* 
     float* os = slices == 1 ? score + (long)b0 * k : cs + (long)b0 * slices * k;
     int32_t* oi = slices == 1 ? idx + (long)b0 * k : ci + (long)b0 * slices * k;
     const float* qsc = q_scale ? q_scale + b0 : nullptr;
-    if (scaled)
-      hipLaunchKernelGGL(sim_topk_kernel<true>, dim3(slices), dim3(512), (size_t)kLds, s, qb + (long)b0 * D, qsc,
-                         (const bf16*)g, g_scale, Bq, N, D, k, os, oi);
-    else
-      hipLaunchKernelGGL(sim_topk_kernel<false>, dim3(slices), dim3(512), (size_t)kLds, s, qb + (long)b0 * D, qsc,
-                         (const bf16*)g, g_scale, Bq, N, D, k, os, oi);
+    const int32_t* qw = q_want ? q_want + b0 : nullptr;
+    auto launch = [&](auto kernel, int lds_bytes) {
+      hipLaunchKernelGGL(kernel, dim3(slices), dim3(512), (size_t)lds_bytes, s, qb + (long)b0 * D, qsc, (const bf16*)g,
+                         g_scale, Bq, N, D, k, os, oi, g_label, qw);
+    };
+    if (g_label) {
+      if (scaled) launch(sim_topk_kernel<true, true>, kLds);
+      else launch(sim_topk_kernel<false, true>, kLds);
+    } else {
+      if (scaled) launch(sim_topk_kernel<true, false>, kLdsPlain);
+      else launch(sim_topk_kernel<false, false>, kLdsPlain);
+    }
     DMLC_HIP_CHECK(hipGetLastError());
   }
   if (slices > 1) {
-    hipLaunchKernelGGL(sim_merge_kernel, dim3((B + 3) / 4), dim3(256), 0, s, (const float*)cs, (const int32_t*)ci, B,
-                       slices, k, idx, score);
+    if (g_label)
+      hipLaunchKernelGGL(sim_merge_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, (const float*)cs,
+                         (const int32_t*)ci, B, slices, k, idx, score);
+    else
+      hipLaunchKernelGGL(sim_merge_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, (const float*)cs,
+                         (const int32_t*)ci, B, slices, k, idx, score);
     DMLC_HIP_CHECK(hipGetLastError());
   }
 }

@@ -985,7 +985,8 @@ def topk_out(out, B: int, k: int, device, what: str):
 
 
 def sim_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, q_scale: torch.Tensor | None = None,
-             g_scale: torch.Tensor | None = None, out=None, slices: int | None = None):
+             g_scale: torch.Tensor | None = None, out=None, slices: int | None = None,
+             g_label: torch.Tensor | None = None, q_want: torch.Tensor | None = None):
     """The k gallery rows nearest to each query (csrc/kernels/sim_topk.hip):
     (idx int32 [B,k], score f32 [B,k]), score(b, n) = (sum_d bf16(q[b,d])
     g[n,d]) q_scale[b] g_scale[n] in descending order, equal scores by
@@ -994,8 +995,15 @@ def sim_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, q_scale: torc
     float32 [B] / [N] or None (1). 1 <= k <= min(N, MAX_TOPK). ``out``: the
     (idx, score) pair to write; ``slices``: how many runs of whole 128-row
     tiles the gallery is cut into (default: about one per CU) - the answer's
-    bits do not depend on it."""
-    _need_cuda(queries, gallery, q_scale, g_scale)
+    bits do not depend on it.
+
+    The row filter: ``g_label`` int32 [N], row n is a candidate only if
+    g_label[n] >= 0 (negative: a removed row); ``q_want`` int32 [B], only with
+    g_label: query b accepts only rows labelled q_want[b] where that is >= 0,
+    any live row otherwise. A query with fewer than k candidates gets idx =
+    -1, score = -inf at the ranks left over, after the real ones. Without
+    g_label: the unfiltered kernel, as before."""
+    _need_cuda(queries, gallery, q_scale, g_scale, g_label, q_want)
     C = native()
     dev = gallery.device
     if gallery.dtype != torch.bfloat16 or gallery.dim() != 2 or not gallery.is_contiguous():
@@ -1012,6 +1020,12 @@ def sim_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, q_scale: torc
         if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (n,) or t.device != dev
                               or not t.is_contiguous()):
             raise ValueError(f"sim_topk: {what} must be contiguous float32 [{n}] on {dev}")
+    if q_want is not None and g_label is None:
+        raise ValueError("sim_topk: q_want needs g_label")
+    for t, n, what in ((g_label, N, "g_label"), (q_want, B, "q_want")):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (n,) or t.device != dev
+                              or not t.is_contiguous()):
+            raise ValueError(f"sim_topk: {what} must be contiguous int32 [{n}] on {dev}")
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
     if slices is None:
         slices = C.sim_topk_slices(B, N, cus)
@@ -1022,8 +1036,49 @@ def sim_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, q_scale: torc
         return idx, score
     ws = _sim_ws(dev, C.sim_topk_ws_bytes(B, k, slices))
     C.sim_topk(_ptr(queries), qdt, _ptr(q_scale), _ptr(gallery), _ptr(g_scale), B, N, D, k, _ptr(idx), _ptr(score),
-               _ptr(ws), ws.numel(), cus, _stream(), slices=slices)
+               _ptr(ws), ws.numel(), cus, _stream(), slices=slices, g_label=_ptr(g_label), q_want=_ptr(q_want))
     return idx, score
+
+
+def knn_vote(idx: torch.Tensor, score: torch.Tensor, g_label: torch.Tensor, weighted: bool = False, out=None):
+    """The k-NN vote over a search's answer (csrc/kernels/knn_vote.hip):
+    (label int32 [B], share f32 [B]). idx int32 / score float32 [B,k], k <=
+    MAX_TOPK; g_label int32 [N]. Rank j votes iff 0 <= idx[b,j] < N, with
+    label g_label[idx[b,j]] and weight 1 or, ``weighted``, max(score[b,j], 0).
+    A label's total is the fp32 sum of its ranks' weights in ascending rank
+    order; the largest total wins, equal totals by the best rank; share = that
+    total / the fp32 sum of all voting weights (0 if that is 0). No voter:
+    (-1, 0). ``out``: the (label, share) pair to write."""
+    _need_cuda(idx, score, g_label)
+    dev = idx.device
+    C = native()
+    if idx.dtype != torch.int32 or idx.dim() != 2 or not idx.is_contiguous() or not 1 <= idx.shape[1] <= C.MAX_TOPK:
+        raise ValueError(f"knn_vote: idx must be contiguous int32 [B,k], k in 1..{C.MAX_TOPK}, got {idx.dtype} "
+                         f"{tuple(idx.shape)}")
+    B, k = idx.shape
+    if score.dtype != torch.float32 or tuple(score.shape) != (B, k) or score.device != dev \
+            or not score.is_contiguous():
+        raise ValueError(f"knn_vote: score must be contiguous float32 [{B},{k}] on {dev}")
+    if g_label.dtype != torch.int32 or g_label.dim() != 1 or g_label.shape[0] < 1 or g_label.device != dev \
+            or not g_label.is_contiguous():
+        raise ValueError(f"knn_vote: g_label must be contiguous int32 [N >= 1] on {dev}")
+    label, share = vote_out(out, B, dev, "knn_vote")
+    if B:
+        C.knn_vote(_ptr(idx), _ptr(score), _ptr(g_label), g_label.shape[0], B, k, bool(weighted), _ptr(label),
+                   _ptr(share), _stream())
+    return label, share
+
+
+def vote_out(out, B: int, device, what: str):
+    """The (label int32 [B], share float32 [B]) pair of a vote: ``out`` checked, or new tensors."""
+    if out is None:
+        return (torch.empty(B, dtype=torch.int32, device=device), torch.empty(B, dtype=torch.float32, device=device))
+    label, share = out
+    for t, dt in ((label, torch.int32), (share, torch.float32)):
+        if t.device != device or t.dtype != dt or tuple(t.shape) != (B,) or not t.is_contiguous():
+            raise ValueError(f"{what}: out expects contiguous {dt} [{B}] on {device}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    return label, share
 
 
 def gallery_pack(rows: torch.Tensor, with_norms: bool = False):

@@ -106,21 +106,30 @@ class InferenceEngine:
             raise ValueError(f"{what}: expected a dmlc.Gallery of dim {self.feature_dim} on {self.device}, got dim "
                              f"{getattr(gallery, 'dim', None)} on {getattr(gallery, 'device', None)}")
 
-    def index(self, images: torch.Tensor, gallery, use_graph: bool = True) -> range:
-        """``gallery.add(self.embed(images))``: store the images' embeddings
-        in a ``dmlc.Gallery`` of this engine's ``feature_dim`` on this GPU;
-        the new rows' ids. images as for ``predict``."""
+    def index(self, images: torch.Tensor, gallery, use_graph: bool = True, labels=None) -> range:
+        """``gallery.add(self.embed(images), labels)``: store the images'
+        embeddings in a ``dmlc.Gallery`` of this engine's ``feature_dim`` on
+        this GPU; the new rows' ids. images as for ``predict``."""
         self._check_gallery(gallery, "index")
-        return gallery.add(self._embed_into_buffer(images, use_graph))
+        return gallery.add(self._embed_into_buffer(images, use_graph), labels)
 
-    def search(self, images: torch.Tensor, gallery, k: int = 1, use_graph: bool = True, out=None):
+    def search(self, images: torch.Tensor, gallery, k: int = 1, use_graph: bool = True, out=None, where=None):
         """The k stored rows nearest to each image: ``gallery.search(
         self.embed(images), k)``, the same bits, with the embeddings in a
         buffer the engine keeps and the search launched on the same stream
         after the forward (whose plan and graphs are what ``embed`` uses).
-        Returns (idx int32 [B,k], score f32 [B,k])."""
+        ``where``: ``Gallery.search``'s label filter. Returns (idx int32
+        [B,k], score f32 [B,k])."""
         self._check_gallery(gallery, "search")
-        return gallery.search(self._embed_into_buffer(images, use_graph), k, out)
+        return gallery.search(self._embed_into_buffer(images, use_graph), k, out, where)
+
+    def classify_knn(self, images: torch.Tensor, gallery, k: int = 5, weighted: bool = False, use_graph: bool = True,
+                     out=None):
+        """k-NN labelling against a gallery: ``gallery.classify(
+        self.embed(images), k, weighted)``, the same bits. Returns (label
+        int32 [B], share f32 [B])."""
+        self._check_gallery(gallery, "classify_knn")
+        return gallery.classify(self._embed_into_buffer(images, use_graph), k, weighted, out)
 
     def _embed_into_buffer(self, images, use_graph):
         B = images.shape[0]

@@ -14,10 +14,22 @@ dmlc.Gallery, InferenceEngine.search), written as plain text. One GPU.
   engine  a graph-replayed ResNet18 b256 embed() alone and engine.search()
           against a 100 k gallery (the same forward, then the search on the
           same stream), interleaved.
+  filtered  the row filter and the k-NN vote (profiles/search_filtered.txt):
+          at D = 512, B = 1 / 256, N = 100 k / 1 M, k = 1 / 16, dot metric,
+          interleaved: the unfiltered launch; the same launch of another
+          build of the library (--base-lib: libdmlc_gpu.so or sim_topk.hip
+          alone built from the commit to compare with, loaded beside this
+          tree's), measured twice so that the run prints the box's own
+          spread; the filter on with every row live, with half the rows
+          removed, and with wanted labels over 1000 classes. Then one
+          knn_vote launch at B = 256, and a graph-replayed ResNet18 b256
+          classify_knn() next to search(), both at k = 5.
 
-usage: python tools/search_bench.py [kernel] [engine] [--blocks 5] [--out profiles/search.txt]
+usage: python tools/search_bench.py [kernel] [engine] [filtered] [--blocks 5] [--base-lib LIB]
+                                    [--out profiles/search.txt]
 """
 import argparse
+import ctypes
 import os
 import statistics
 import sys
@@ -131,10 +143,126 @@ def bench_engine(a, emit):
     emit(f"  added by the search     {ms - me:9.1f} us = {(ms - me) / me * 100:.1f} % of the forward")
 
 
+# dmlc::sim_topk as it was before the row filter's two trailing arguments
+_BASE_SYMBOL = "_ZN4dmlc8sim_topkEPKvNS_11TensorDTypeEPKfS1_S4_iliiPiPfPvmiP12ihipStream_ti"
+
+
+def _base_sim_topk(path):
+    """The unfiltered launcher of another build of the library, or None."""
+    if not path:
+        return None
+    fn = getattr(ctypes.CDLL(os.path.abspath(path), mode=ctypes.RTLD_LOCAL), _BASE_SYMBOL)
+    vp = ctypes.c_void_p
+    fn.argtypes = [vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int, vp, vp, vp,
+                   ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_int]
+    fn.restype = None
+    return fn
+
+
+def bench_filtered(a, emit):
+    dev = torch.device("cuda", 0)
+    C = dmlc.native()
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    stream = torch.cuda.current_stream().cuda_stream
+    base = _base_sim_topk(a.base_lib)
+    D, BF = 512, C.TensorDType.BF16
+    emit(f"filtered search ({torch.cuda.get_device_name(0)}, {cus} CUs), D = {D}, dot metric, bf16 randn, native "
+         f"launcher on preallocated outputs; device events around back-to-back launches, median (min - max) of "
+         f"{a.blocks} interleaved blocks. base / base again: the unfiltered launch of the build to compare with "
+         f"({'given' if base else 'not given: --base-lib'}), measured twice in the same turns: their difference is "
+         f"the box's spread. live: filter on, every row live; half: 50 % of the rows removed; classes: wanted "
+         f"labels over 1000 classes, nothing removed:")
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for N in (100_000, 1_000_000):
+        g = ops.gallery_pack(torch.randn(N, D, device=dev, generator=gen))
+        live = torch.zeros(N, dtype=torch.int32, device=dev)
+        half = torch.where(torch.rand(N, device=dev, generator=gen) < 0.5, -1, 0).to(torch.int32)
+        classes = torch.randint(0, 1000, (N,), device=dev, generator=gen).to(torch.int32)
+        for B in (1, 256):
+            qb = ops.gallery_pack(torch.randn(B, D, device=dev, generator=gen))
+            want = torch.randint(0, 1000, (B,), device=dev, generator=gen).to(torch.int32)
+            for k in (1, 16):
+                slices = C.sim_topk_slices(B, N, cus)
+                ws = torch.empty(C.sim_topk_ws_bytes(B, k, slices), dtype=torch.uint8, device=dev)
+                idx = torch.empty(B, k, dtype=torch.int32, device=dev)
+                score = torch.empty(B, k, dtype=torch.float32, device=dev)
+
+                def run(label=None, q_want=None):
+                    C.sim_topk(qb.data_ptr(), BF, 0, g.data_ptr(), 0, B, N, D, k, idx.data_ptr(), score.data_ptr(),
+                               ws.data_ptr(), ws.numel(), cus, stream, g_label=0 if label is None else label.data_ptr(),
+                               q_want=0 if q_want is None else q_want.data_ptr())
+
+                def run_base():
+                    base(qb.data_ptr(), int(BF), None, g.data_ptr(), None, B, N, D, k, idx.data_ptr(),
+                         score.data_ptr(), ws.data_ptr(), ws.numel(), cus, stream, 0)
+                fns = {}
+                if base:
+                    run_base()
+                    torch.cuda.synchronize()
+                    theirs = (idx.clone(), score.clone())
+                    run()
+                    torch.cuda.synchronize()
+                    if not (torch.equal(theirs[0], idx) and torch.equal(theirs[1], score)):
+                        raise SystemExit("search_bench: the unfiltered launch and the base build's differ in bits")
+                    fns["base"] = run_base
+                fns["unfiltered"] = run
+                if base:
+                    fns["base again"] = run_base
+                fns["live"] = lambda: run(live)
+                fns["half"] = lambda: run(half)
+                fns["classes"] = lambda: run(classes, want)
+                t = _interleaved(fns, a.blocks)
+                ref = statistics.median(t["unfiltered"])
+                for name in fns:
+                    m = statistics.median(t[name])
+                    emit(f"  N={N:<8} B={B:<4} k={k:<3} {name:<11} {_fmt(t[name])}  {m / ref:6.3f} x unfiltered  "
+                         f"{N * D * 2 / m / 1e6:6.3f} TB/s  slices {slices}")
+                if base:
+                    b1, b2 = statistics.median(t["base"]), statistics.median(t["base again"])
+                    emit(f"  {'':<24} spread of the base build: {abs(b1 - b2) / min(b1, b2) * 100:.2f} % between its "
+                         f"two medians; unfiltered is {(ref / ((b1 + b2) / 2) - 1) * 100:+.2f} % off their mean")
+        del g, live, half, classes
+    # the vote alone
+    B, N = 256, 100_000
+    labels = torch.randint(0, 1000, (N,), device=dev, generator=gen).to(torch.int32)
+    for k in (5, 16):
+        idx = torch.randint(0, N, (B, k), device=dev, generator=gen).to(torch.int32)
+        score = torch.rand(B, k, device=dev, generator=gen)
+        out = (torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, device=dev))
+        fns = {w: (lambda w=w: C.knn_vote(idx.data_ptr(), score.data_ptr(), labels.data_ptr(), N, B, k, w == "weighted",
+                                          out[0].data_ptr(), out[1].data_ptr(), stream))
+               for w in ("uniform", "weighted")}
+        t = _interleaved(fns, a.blocks)
+        for name in fns:
+            emit(f"  knn_vote B={B} k={k:<3} {name:<9} {_fmt(t[name])} per launch (back to back)")
+    # the engine
+    from dmlc.models.calibrated import mixed_images
+    from dmlc.runtime import InferenceEngine
+    eng = InferenceEngine("resnet18", None, max_batch=B)
+    img = mixed_images(B, seed=1).to(dev)
+    gal = dmlc.Gallery(eng.feature_dim, N, max_batch=B)
+    for i in range(0, N, 10_000):
+        gal.add(torch.randn(10_000, eng.feature_dim, device=dev, generator=gen).abs(), labels=labels[i:i + 10_000])
+    sout = (torch.empty(B, 5, dtype=torch.int32, device=dev), torch.empty(B, 5, device=dev))
+    cout = (torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, device=dev))
+    fns = {"search": lambda: eng.search(img, gal, k=5, out=sout),
+           "classify_knn": lambda: eng.classify_knn(img, gal, k=5, out=cout)}
+    t = _interleaved(fns, a.blocks)
+    emit(f"engine, resnet18 b{B} graph replay, gallery of {N} x {eng.feature_dim} (cosine, 1000 labels, k = 5):")
+    for name in fns:
+        emit(f"  {name + '()':<15} {_fmt(t[name])} per batch  {B / statistics.median(t[name]) * 1e6:9.0f} images/s")
+    gal.remove(range(0, N, 2))
+    t = _interleaved(fns, a.blocks)
+    emit("  the same with every second row removed (the filtered kernel):")
+    for name in fns:
+        emit(f"  {name + '()':<15} {_fmt(t[name])} per batch  {B / statistics.median(t[name]) * 1e6:9.0f} images/s")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", nargs="*", default=["kernel", "engine"], help="kernel, engine")
+    ap.add_argument("what", nargs="*", default=["kernel", "engine"], help="kernel, engine, filtered")
     ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--base-lib", default="", help="filtered: a library built from the commit to compare with")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -150,6 +278,8 @@ def main():
             bench_kernel(a, emit)
         elif w == "engine":
             bench_engine(a, emit)
+        elif w == "filtered":
+            bench_filtered(a, emit)
         else:
             raise SystemExit(f"unknown measurement: {w}")
     if a.out:
