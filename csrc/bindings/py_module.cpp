@@ -496,14 +496,40 @@ PYBIND11_MODULE(_C, m) {
     gallery_pack(P<float>(rows), P<void>(g), P<float>(inv_norm), M, D, S(stream));
   }, py::arg("rows"), py::arg("g"), py::arg("inv_norm"), py::arg("M"), py::arg("D"), py::arg("stream"),
         py::call_guard<py::gil_scoped_release>());
+  // the e4m3 gallery (sim_topk.hip): quantiser and search
+  m.def("sim_topk8_supported", &sim_topk8_supported, py::arg("D"));
+  m.def("sim_topk8_ws_bytes", &sim_topk8_ws_bytes, py::arg("B"), py::arg("k"), py::arg("slices"));
+  m.def("gallery_pack8", [](uintptr_t rows, TensorDType dt, uintptr_t codes, uintptr_t scale, bool cosine, int M, int D,
+                            uintptr_t stream) {
+    gallery_pack8(P<void>(rows), dt, P<void>(codes), P<float>(scale), cosine, M, D, S(stream));
+  }, py::arg("rows"), py::arg("dtype"), py::arg("codes"), py::arg("scale"), py::arg("cosine"), py::arg("M"),
+        py::arg("D"), py::arg("stream"), py::call_guard<py::gil_scoped_release>());
+  m.def("sim_topk8", [](uintptr_t q, TensorDType qdt, uintptr_t g_codes, uintptr_t g_scale, bool cosine, int B, long N,
+                        int D, int k, uintptr_t idx, uintptr_t score, uintptr_t ws, size_t ws_bytes, int num_cus,
+                        uintptr_t stream, int slices, uintptr_t g_label, uintptr_t q_want) {
+    sim_topk8(P<void>(q), qdt, P<void>(g_codes), P<float>(g_scale), cosine, B, N, D, k, P<int32_t>(idx),
+              P<float>(score), P<void>(ws), ws_bytes, num_cus, S(stream), slices, P<int32_t>(g_label),
+              P<int32_t>(q_want));
+  }, py::arg("q"), py::arg("dtype"), py::arg("g_codes"), py::arg("g_scale"), py::arg("cosine"), py::arg("B"),
+        py::arg("N"), py::arg("D"), py::arg("k"), py::arg("idx"), py::arg("score"), py::arg("ws"), py::arg("ws_bytes"),
+        py::arg("num_cus"), py::arg("stream"), py::arg("slices") = 0, py::arg("g_label") = 0, py::arg("q_want") = 0,
+        py::call_guard<py::gil_scoped_release>());
   py::class_<Gallery>(m, "Gallery")
-      .def(py::init([](int dim, long capacity, int device, const std::string& metric, int max_batch) {
+      .def(py::init([](int dim, long capacity, int device, const std::string& metric, int max_batch,
+                       const std::string& dtype) {
              if (metric != "cosine" && metric != "dot")
                throw std::invalid_argument("Gallery: metric is \"cosine\" or \"dot\", got " + metric);
-             return new Gallery(dim, capacity, device, metric == "cosine", max_batch);
+             if (dtype != "bf16" && dtype != "e4m3")
+               throw std::invalid_argument("Gallery: dtype is \"bf16\" or \"e4m3\", got " + dtype);
+             return new Gallery(dim, capacity, device, metric == "cosine", max_batch,
+                                dtype == "e4m3" ? GalleryDType::E4M3 : GalleryDType::BF16);
            }),
            py::arg("dim"), py::arg("capacity"), py::arg("device") = 0, py::arg("metric") = "cosine",
-           py::arg("max_batch") = 256)
+           py::arg("max_batch") = 256, py::arg("dtype") = "bf16")
+      .def_property_readonly("dtype",
+                             [](const Gallery& g) {
+                               return std::string(g.dtype() == GalleryDType::E4M3 ? "e4m3" : "bf16");
+                             })
       .def_property_readonly("dim", &Gallery::dim)
       .def_property_readonly("capacity", &Gallery::capacity)
       .def_property_readonly("device", &Gallery::device)

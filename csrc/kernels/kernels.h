@@ -493,6 +493,33 @@ void sim_topk(const void* q, TensorDType qdt /*F32 or BF16*/, const float* q_sca
               int32_t* idx /*[B,k]*/, float* score /*[B,k]*/, void* ws, size_t ws_bytes, int num_cus, hipStream_t s,
               int slices_override = 0, const int32_t* g_label /*[N] or null*/ = nullptr,
               const int32_t* q_want /*[B] or null*/ = nullptr);
+// The same search over an e4m3 gallery (one byte per element) on the
+// block-scaled fp8 MFMA. The quantisation rule, for gallery rows and queries
+// alike: for a finite row v (bf16 widened exactly), amax = max |v_d|, e the
+// largest integer with amax 2^e <= 448 (amax = m 2^x, 1 <= m < 2: e = 8 - x
+// if m <= 1.75, else 7 - x), clamped to [-126, 126], 0 if amax == 0; codes
+// c_d = e4m3_rne(v_d 2^e), OCP e4m3fn, subnormals kept (the multiply is exact
+// and nothing exceeds 448). The row's fp32 scale: 2^-e (dot), or
+// 1 / max(sqrt(sum c_d^2), 1e-12) on the codes with gallery_pack's arithmetic
+// (cosine: the power of two cancels).
+//   score(b, n) = ((sum_d cq[b][d] cg[n][d]) q_scale[b]) g_scale[n]
+// with exact products, one wave summing the whole of D in one order, then the
+// two fp32 multiplies in that order; order, ties, empty slots, slices and the
+// row filter are sim_topk's. D % 128 == 0, 128 <= D <= 4096.
+// gallery_pack8: rows fp32 or bf16 [M, D] -> codes [M, D] and scale [M]; rows
+// and codes 16-B aligned. sim_topk8 quantises the queries with it into ws on
+// s, then searches: q fp32 or bf16 [B, D]; g_codes [N, D], g_scale [N] (as
+// gallery_pack8 made them under the same metric); q, g_codes and ws 16-B
+// aligned; ws: sim_topk8_ws_bytes(B, k, slices). No allocation, no
+// synchronisation. The slice helpers above are shared.
+bool sim_topk8_supported(int D);  // D % 128 == 0, 128 <= D <= 4096
+size_t sim_topk8_ws_bytes(int B, int k, int slices);
+void gallery_pack8(const void* rows, TensorDType dt /*F32 or BF16*/, void* codes, float* scale, bool cosine, int M,
+                   int D, hipStream_t s);
+void sim_topk8(const void* q, TensorDType qdt /*F32 or BF16*/, const void* g_codes /*e4m3 [N, D]*/,
+               const float* g_scale /*[N]*/, bool cosine, int B, long N, int D, int k, int32_t* idx /*[B,k]*/,
+               float* score /*[B,k]*/, void* ws, size_t ws_bytes, int num_cus, hipStream_t s, int slices_override = 0,
+               const int32_t* g_label /*[N] or null*/ = nullptr, const int32_t* q_want /*[B] or null*/ = nullptr);
 // labels[ids[i]] = -1 for i < M: marks gallery rows removed. ids in 0..N-1
 // (the caller checks them; an id outside is skipped).
 void gallery_unlabel(int32_t* labels, const int32_t* ids, int M, long N, hipStream_t s);

@@ -62,6 +62,26 @@
 // (this kernel at one slice, else the merge) turns their INT_MAX into -1.
 // The FILTER = false instantiations are the unfiltered kernels unchanged.
 //
+// The e4m3 gallery (FP8): one byte per element. A row is stored as OCP e4m3fn
+// codes c = e4m3_rne(v 2^e), e the largest integer with max|v| 2^e <= 448
+// (clamped to +-126; 0 for a zero row), and one fp32 scale: 2^-e (dot) or
+// 1 / max(sqrt(sum c^2), 1e-12) (cosine: the power of two cancels). Queries
+// are quantised by the same rule (gallery_pack8, into the workspace), and
+// score(b, n) = ((sum_d cq[b][d] cg[n][d]) q_scale[b]) g_scale[n] on
+// v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales, at twice the bf16
+// rate per clock and half the bytes. The stage geometry is byte-identical: a
+// 128-B LDS row holds a K block of 128 codes, and a lane's operand is chunks
+// fq and fq + 4 of its row (the pair that keeps the 16 lanes of a ds_read_b128
+// group on distinct banks under the row swizzle: chunks 2 fq, 2 fq + 1 would
+// pair lanes whose chunk numbers differ in bit 1 only). The MFMA takes lane
+// (fr, fq)'s 32 bytes as K = 32 fq .. 32 fq + 31 of its row; both operands
+// read the same chunks, so which K a byte stands for cancels in the sum.
+// Selection, filter, slices and the merge are the bf16 kernel's code.
+//
+// gallery_pack8: one wave per row; pass 1 finds max|v| across the wave, pass 2
+// scales (exact), converts with v_cvt_pk_fp8_f32 and sums the squares of the
+// decoded codes as gallery_pack does.
+//
 // gallery_pack: fp32 rows -> bf16 (nearest even), optionally with
 // 1 / max(sqrt(sum v^2), 1e-12) of the rounded values v (fp32 squares summed
 // per lane and across the wave; IEEE root and divide): embed.hip's
@@ -71,6 +91,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <type_traits>
 
 namespace dmlc {
 
@@ -80,7 +101,8 @@ typedef int intx4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBQ = 256;  // queries per workgroup
 constexpr int kBG = 128;  // gallery rows per tile
-constexpr int kKB = 64;   // K block per stage
+constexpr int kKB = 64;   // K block per stage (bf16)
+constexpr int kKB8 = 128;  // K block per stage (e4m3): the same 128 bytes a row
 constexpr int kGB = kBG * kKB * 2;  // 16 KB gallery stage
 constexpr int kQB = kBQ * kKB * 2;  // 32 KB query stage
 constexpr int kStage = kGB + kQB;
@@ -123,14 +145,22 @@ __device__ __forceinline__ void list_insert(float* ls, int* li, int k, float s, 
 // q: bf16 [Bq, D], this block's queries; g: bf16 [N, D]. Slice blockIdx.x of
 // gridDim.x takes tiles [t0, t1). out_s / out_i: [Bq][gridDim.x][k].
 // FILTER: g_label [N] (never null), q_want [Bq] or null.
-template <bool SCALED, bool FILTER>
-__global__ __launch_bounds__(512, 1) void sim_topk_kernel(const bf16* __restrict__ q, const float* __restrict__ q_scale,
-                                                          const bf16* __restrict__ g,
+// FP8: q and g hold e4m3 codes (D % 128 == 0), both scales are given.
+template <bool FP8>
+using sim_elem = typename std::conditional<FP8, uint8_t, bf16>::type;
+
+template <bool SCALED, bool FILTER, bool FP8 = false>
+__global__ __launch_bounds__(512, 1) void sim_topk_kernel(const sim_elem<FP8>* __restrict__ q,
+                                                          const float* __restrict__ q_scale,
+                                                          const sim_elem<FP8>* __restrict__ g,
                                                           const float* __restrict__ g_scale, int Bq, long N, int D,
                                                           int k, float* __restrict__ out_s,
                                                           int32_t* __restrict__ out_i,
                                                           const int32_t* __restrict__ g_label,
                                                           const int32_t* __restrict__ q_want) {
+  static_assert(!FP8 || SCALED, "e4m3 codes always come with their scales");
+  constexpr int KB = FP8 ? kKB8 : kKB;  // K elements per stage
+  constexpr int CE = FP8 ? 16 : 8;      // elements per 16-B chunk
   extern __shared__ __attribute__((aligned(16))) uint4 smem[];
   char* lds = (char*)smem;
   float* ls = (float*)(lds + kListS);
@@ -145,7 +175,7 @@ __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const bf16* __restrict
   const long base_t = tiles / slices, rem = tiles % slices;
   const long t0 = slice * base_t + (slice < rem ? slice : rem);
   const int nt = (int)(base_t + (slice < rem ? 1 : 0));
-  const int nk = (D + kKB - 1) / kKB;
+  const int nk = (D + KB - 1) / KB;
   const bool active = 32 * wave < Bq;  // (wave-uniform)
 
   // this wave's lists start empty; without g_scale the scale buffer holds ones
@@ -172,13 +202,13 @@ __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const bf16* __restrict
   // vmcnt(0), so the waves need not issue the same number.
   auto dma_stage = [&](long tile, int kb, int slot) __attribute__((always_inline)) {
     char* base = lds + slot * kStage;
-    const int k0 = kb * kKB;
+    const int k0 = kb * KB;
     const long n0 = tile * kBG;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int p = (2 * wave + j) * 64 + lane, r = p >> 3;
-      int kc = k0 + 8 * ((p & 7) ^ (r & 7));
-      if (kc >= D) kc -= 32;  // (the absent half of a last block of 32)
+      int kc = k0 + CE * ((p & 7) ^ (r & 7));
+      if (!FP8 && kc >= D) kc -= 32;  // (the absent half of a last block of 32)
       const long row = n0 + r < N ? n0 + r : N - 1;
       dma16(g + row * D + kc, base + (2 * wave + j) * 1024);
     }
@@ -187,8 +217,8 @@ __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const bf16* __restrict
       const int i = 4 * wave + j;
       if (8 * i < Bq) {
         const int p = i * 64 + lane, r = p >> 3;
-        int kc = k0 + 8 * ((p & 7) ^ (r & 7));
-        if (kc >= D) kc -= 32;
+        int kc = k0 + CE * ((p & 7) ^ (r & 7));
+        if (!FP8 && kc >= D) kc -= 32;
         const int row = r < Bq ? r : Bq - 1;
         dma16(q + (long)row * D + kc, base + kGB + i * 1024);
       }
@@ -221,20 +251,40 @@ __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const bf16* __restrict
     else if (t + 1 < nt) dma_stage(t0 + t + 1, 0, slot ^ 1);
     if (active) {
       const char* base = lds + slot * kStage;
+      if constexpr (FP8) {
+        // the whole K block in one MFMA per fragment pair: chunks fq and fq + 4 of each row
+        auto frag = [&](const char* region, int row) __attribute__((always_inline)) {
+          const uint4 lo = *(const uint4*)(region + st_off(row, fq));
+          const uint4 hi = *(const uint4*)(region + st_off(row, fq + 4));
+          return v8i{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+        };
+        v8i gfr[8], qfr[2];
 #pragma unroll
-      for (int kk = 0; kk < kKB / 32; ++kk) {
-        if (kb * kKB + 32 * kk < D) {  // (uniform)
-          bf16x8 gfr[8], qfr[2];
+        for (int gf = 0; gf < 8; ++gf) gfr[gf] = frag(base, 16 * gf + fr);
 #pragma unroll
-          for (int gf = 0; gf < 8; ++gf) gfr[gf] = *(const bf16x8*)(base + st_off(16 * gf + fr, 4 * kk + fq));
+        for (int qf = 0; qf < 2; ++qf) qfr[qf] = frag(base + kGB, 32 * wave + 16 * qf + fr);
+#pragma unroll
+        for (int gf = 0; gf < 8; ++gf)
 #pragma unroll
           for (int qf = 0; qf < 2; ++qf)
-            qfr[qf] = *(const bf16x8*)(base + kGB + st_off(32 * wave + 16 * qf + fr, 4 * kk + fq));
+            acc[gf][qf] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(gfr[gf], qfr[qf], acc[gf][qf], 0, 0, 0, 127,
+                                                                           0, 127);
+      } else {
 #pragma unroll
-          for (int gf = 0; gf < 8; ++gf)
+        for (int kk = 0; kk < kKB / 32; ++kk) {
+          if (kb * kKB + 32 * kk < D) {  // (uniform)
+            bf16x8 gfr[8], qfr[2];
+#pragma unroll
+            for (int gf = 0; gf < 8; ++gf) gfr[gf] = *(const bf16x8*)(base + st_off(16 * gf + fr, 4 * kk + fq));
 #pragma unroll
             for (int qf = 0; qf < 2; ++qf)
-              acc[gf][qf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gfr[gf], qfr[qf], acc[gf][qf], 0, 0, 0);
+              qfr[qf] = *(const bf16x8*)(base + kGB + st_off(32 * wave + 16 * qf + fr, 4 * kk + fq));
+#pragma unroll
+            for (int gf = 0; gf < 8; ++gf)
+#pragma unroll
+              for (int qf = 0; qf < 2; ++qf)
+                acc[gf][qf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gfr[gf], qfr[qf], acc[gf][qf], 0, 0, 0);
+          }
         }
       }
     }
@@ -435,6 +485,64 @@ __global__ __launch_bounds__(256) void gallery_pack_kernel(const void* __restric
   }
 }
 
+// 8 consecutive values of row m as fp32 (a bf16 input widens exactly)
+template <bool IN_BF16>
+__device__ __forceinline__ void load8(const void* rows, long at, float* v) {
+  if constexpr (IN_BF16) {
+    unpack8(*(const uint4*)((const bf16*)rows + at), v);
+  } else {
+    const float4* src = (const float4*)((const float*)rows + at);
+    const float4 lo = src[0], hi = src[1];
+    v[0] = lo.x, v[1] = lo.y, v[2] = lo.z, v[3] = lo.w;
+    v[4] = hi.x, v[5] = hi.y, v[6] = hi.z, v[7] = hi.w;
+  }
+}
+
+// The e4m3 quantiser: one wave per row, 4 rows a workgroup, a lane owns
+// 8-element groups lane, lane + 64, ... (16- or 32-B loads, 8-B stores).
+// scale[m] = 2^-e (dot) or the inverse norm of the codes (cosine).
+template <bool IN_BF16>
+__global__ __launch_bounds__(256) void gallery_pack8_kernel(const void* __restrict__ rows, uint8_t* __restrict__ codes,
+                                                            float* __restrict__ scale, int M, int D, bool cosine) {
+  const int lane = threadIdx.x & 63;
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m >= M) return;
+  float amax = 0.f;
+  for (int c = lane * 8; c < D; c += 512) {
+    float v[8];
+    load8<IN_BF16>(rows, (long)m * D + c, v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+  }
+  amax = wave_max(amax);
+  // amax = m 2^x, 1 <= m < 2: e = 8 - x, one less if m > 1.75 (448 = 1.75 2^8); a subnormal amax clamps at 126
+  const uint32_t ab = __float_as_uint(amax);
+  const int x = (int)(ab >> 23) - 127;
+  int e = (ab & 0x7fffffu) <= 0x600000u ? 8 - x : 7 - x;
+  e = e > 126 ? 126 : e;  // (e >= -120 for any finite amax)
+  if (ab == 0) e = 0;
+  const float up = __uint_as_float((uint32_t)(127 + e) << 23);  // 2^e
+  float ss = 0.f;
+  for (int c = lane * 8; c < D; c += 512) {
+    float v[8];
+    load8<IN_BF16>(rows, (long)m * D + c, v);
+    u32x2 p;
+    p.x = e4m3x4_from_f32(v[0] * up, v[1] * up, v[2] * up, v[3] * up);
+    p.y = e4m3x4_from_f32(v[4] * up, v[5] * up, v[6] * up, v[7] * up);
+    *(u32x2*)(codes + (long)m * D + c) = p;
+    e4m3x4_to_f32(p.x, v);
+    e4m3x4_to_f32(p.y, v + 4);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ss += v[j] * v[j];
+  }
+  if (cosine) {  // (uniform)
+    ss = wave_sum(ss);
+    if (lane == 0) scale[m] = 1.f / fmaxf(sqrtf(ss), 1e-12f);
+  } else if (lane == 0) {
+    scale[m] = __uint_as_float((uint32_t)(127 - e) << 23);  // 2^-e
+  }
+}
+
 // labels[ids[i]] = -1: a removed row (equal ids write the same value)
 __global__ __launch_bounds__(256) void gallery_unlabel_kernel(int32_t* __restrict__ labels,
                                                               const int32_t* __restrict__ ids, int M, long N) {
@@ -447,6 +555,46 @@ __global__ __launch_bounds__(256) void gallery_unlabel_kernel(int32_t* __restric
 long sim_tiles(long N) { return (N + kBG - 1) / kBG; }
 
 size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+
+// The search launches on prepared operands: one per block of 256 queries, then the merge.
+template <bool FP8>
+void launch_search(const sim_elem<FP8>* qb, const float* q_scale, const sim_elem<FP8>* g, const float* g_scale, int B,
+                   long N, int D, int k, int32_t* idx, float* score, float* cs, int32_t* ci, int slices,
+                   const int32_t* g_label, const int32_t* q_want, hipStream_t s) {
+  const bool scaled = q_scale || g_scale;
+  for (int b0 = 0; b0 < B; b0 += kBQ) {  // blocks of 256 queries
+    const int Bq = std::min(kBQ, B - b0);
+    // one slice: the lists are the answer ([Bq][1][k] = [Bq][k])
+    float* os = slices == 1 ? score + (long)b0 * k : cs + (long)b0 * slices * k;
+    int32_t* oi = slices == 1 ? idx + (long)b0 * k : ci + (long)b0 * slices * k;
+    const float* qsc = q_scale ? q_scale + b0 : nullptr;
+    const int32_t* qw = q_want ? q_want + b0 : nullptr;
+    auto launch = [&](auto kernel, int lds_bytes) {
+      hipLaunchKernelGGL(kernel, dim3(slices), dim3(512), (size_t)lds_bytes, s, qb + (long)b0 * D, qsc, g, g_scale, Bq,
+                         N, D, k, os, oi, g_label, qw);
+    };
+    if constexpr (FP8) {
+      if (g_label) launch(sim_topk_kernel<true, true, true>, kLds);
+      else launch(sim_topk_kernel<true, false, true>, kLdsPlain);
+    } else if (g_label) {
+      if (scaled) launch(sim_topk_kernel<true, true>, kLds);
+      else launch(sim_topk_kernel<false, true>, kLds);
+    } else {
+      if (scaled) launch(sim_topk_kernel<true, false>, kLdsPlain);
+      else launch(sim_topk_kernel<false, false>, kLdsPlain);
+    }
+    DMLC_HIP_CHECK(hipGetLastError());
+  }
+  if (slices > 1) {
+    if (g_label)
+      hipLaunchKernelGGL(sim_merge_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, (const float*)cs,
+                         (const int32_t*)ci, B, slices, k, idx, score);
+    else
+      hipLaunchKernelGGL(sim_merge_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, (const float*)cs,
+                         (const int32_t*)ci, B, slices, k, idx, score);
+    DMLC_HIP_CHECK(hipGetLastError());
+  }
+}
 
 }  // namespace
 
@@ -473,6 +621,14 @@ size_t sim_topk_ws_bytes(int B, int k, int slices) {
   if (B < 0 || k < 0 || slices < 0) throw std::invalid_argument("sim_topk_ws_bytes: negative argument");
   // the candidates' scores and rows [B][slices][k], then the queries as bf16 at the widest D
   return 2 * align256((size_t)slices * B * k * 4) + (size_t)B * kMaxD * 2;
+}
+
+bool sim_topk8_supported(int D) { return D >= kKB8 && D <= kMaxD && D % kKB8 == 0; }
+
+size_t sim_topk8_ws_bytes(int B, int k, int slices) {
+  if (B < 0 || k < 0 || slices < 0) throw std::invalid_argument("sim_topk8_ws_bytes: negative argument");
+  // the candidates as above, then the queries' codes at the widest D and their scales
+  return 2 * align256((size_t)slices * B * k * 4) + (size_t)B * (kMaxD + 4);
 }
 
 void gallery_pack(const float* rows, void* g, float* inv_norm, int M, int D, hipStream_t s) {
@@ -530,36 +686,52 @@ void sim_topk(const void* q, TensorDType qdt, const float* q_scale, const void* 
     gallery_pack((const float*)q, packed, nullptr, B, D, s);
     qb = (const bf16*)packed;
   }
-  const bool scaled = q_scale || g_scale;
-  for (int b0 = 0; b0 < B; b0 += kBQ) {  // blocks of 256 queries
-    const int Bq = std::min(kBQ, B - b0);
-    // one slice: the lists are the answer ([Bq][1][k] = [Bq][k])
-    float* os = slices == 1 ? score + (long)b0 * k : cs + (long)b0 * slices * k;
-    int32_t* oi = slices == 1 ? idx + (long)b0 * k : ci + (long)b0 * slices * k;
-    const float* qsc = q_scale ? q_scale + b0 : nullptr;
-    const int32_t* qw = q_want ? q_want + b0 : nullptr;
-    auto launch = [&](auto kernel, int lds_bytes) {
-      hipLaunchKernelGGL(kernel, dim3(slices), dim3(512), (size_t)lds_bytes, s, qb + (long)b0 * D, qsc, (const bf16*)g,
-                         g_scale, Bq, N, D, k, os, oi, g_label, qw);
-    };
-    if (g_label) {
-      if (scaled) launch(sim_topk_kernel<true, true>, kLds);
-      else launch(sim_topk_kernel<false, true>, kLds);
-    } else {
-      if (scaled) launch(sim_topk_kernel<true, false>, kLdsPlain);
-      else launch(sim_topk_kernel<false, false>, kLdsPlain);
-    }
-    DMLC_HIP_CHECK(hipGetLastError());
-  }
-  if (slices > 1) {
-    if (g_label)
-      hipLaunchKernelGGL(sim_merge_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, (const float*)cs,
-                         (const int32_t*)ci, B, slices, k, idx, score);
-    else
-      hipLaunchKernelGGL(sim_merge_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, (const float*)cs,
-                         (const int32_t*)ci, B, slices, k, idx, score);
-    DMLC_HIP_CHECK(hipGetLastError());
-  }
+  launch_search<false>(qb, q_scale, (const bf16*)g, g_scale, B, N, D, k, idx, score, cs, ci, slices, g_label, q_want, s);
+}
+
+void gallery_pack8(const void* rows, TensorDType dt, void* codes, float* scale, bool cosine, int M, int D,
+                   hipStream_t s) {
+  if (!sim_topk8_supported(D)) throw std::invalid_argument("gallery_pack8: needs D % 128 == 0, 128 <= D <= 4096");
+  if (dt != TensorDType::F32 && dt != TensorDType::BF16) throw std::invalid_argument("gallery_pack8: rows are fp32 or bf16");
+  if (M < 0) throw std::invalid_argument("gallery_pack8: M < 0");
+  if (M == 0) return;
+  if (!rows || !codes || !scale || (((uintptr_t)rows | (uintptr_t)codes) & 15))
+    throw std::invalid_argument("gallery_pack8: null / misaligned rows or codes (16 B) or null scale");
+  if (dt == TensorDType::BF16)
+    hipLaunchKernelGGL(gallery_pack8_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, s, rows, (uint8_t*)codes, scale, M,
+                       D, cosine);
+  else
+    hipLaunchKernelGGL(gallery_pack8_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, s, rows, (uint8_t*)codes, scale, M,
+                       D, cosine);
+  DMLC_HIP_CHECK(hipGetLastError());
+}
+
+void sim_topk8(const void* q, TensorDType qdt, const void* g_codes, const float* g_scale, bool cosine, int B, long N,
+               int D, int k, int32_t* idx, float* score, void* ws, size_t ws_bytes, int num_cus, hipStream_t s,
+               int slices_override, const int32_t* g_label, const int32_t* q_want) {
+  if (!sim_topk8_supported(D)) throw std::invalid_argument("sim_topk8: needs D % 128 == 0, 128 <= D <= 4096");
+  if (qdt != TensorDType::F32 && qdt != TensorDType::BF16) throw std::invalid_argument("sim_topk8: queries are fp32 or bf16");
+  if (B < 0) throw std::invalid_argument("sim_topk8: B < 0");
+  if (N < 1 || N > INT_MAX) throw std::invalid_argument("sim_topk8: N outside 1..2^31 - 1");
+  if (k < 1 || k > N || k > kMaxTopK) throw std::invalid_argument("sim_topk8: k must be in 1..min(N, kMaxTopK)");
+  if (q_want && !g_label) throw std::invalid_argument("sim_topk8: q_want needs g_label");
+  if (B == 0) return;
+  if (!q || !g_codes || !g_scale || !idx || !score || !ws ||
+      (((uintptr_t)q | (uintptr_t)g_codes | (uintptr_t)ws) & 15))
+    throw std::invalid_argument("sim_topk8: null / misaligned operand (q, g_codes and ws need 16 B; g_scale is required)");
+  const int slices = slices_override ? slices_override : sim_topk_slices(B, N, num_cus);
+  if (slices < 1 || slices > sim_topk_max_slices(N))
+    throw std::invalid_argument("sim_topk8: slices outside 1..min(tiles, 512)");
+  if (ws_bytes < sim_topk8_ws_bytes(B, k, slices)) throw std::invalid_argument("sim_topk8: workspace too small");
+  const size_t cand = align256((size_t)slices * B * k * 4);
+  float* cs = (float*)ws;
+  int32_t* ci = (int32_t*)((char*)ws + cand);
+  // the queries' codes [B][D] and scales [B], where the bf16 search keeps its packed queries
+  uint8_t* qc = (uint8_t*)ws + 2 * cand;
+  float* qs = (float*)(qc + (size_t)B * kMaxD);
+  gallery_pack8(q, qdt, qc, qs, cosine, B, D, s);
+  launch_search<true>(qc, qs, (const uint8_t*)g_codes, g_scale, B, N, D, k, idx, score, cs, ci, slices, g_label, q_want,
+                      s);
 }
 
 }  // namespace dmlc

@@ -6,8 +6,11 @@
 
 namespace dmlc {
 
-Gallery::Gallery(int dim, long capacity, int device, bool cosine, int max_batch)
-    : dim_(dim), device_(device), max_batch_(max_batch), capacity_(capacity), cosine_(cosine) {
+Gallery::Gallery(int dim, long capacity, int device, bool cosine, int max_batch, GalleryDType dtype)
+    : dim_(dim), device_(device), max_batch_(max_batch), capacity_(capacity), cosine_(cosine), dtype_(dtype) {
+  const bool e4m3 = dtype_ == GalleryDType::E4M3;
+  if (e4m3 && !sim_topk8_supported(dim))
+    throw std::invalid_argument("Gallery: an e4m3 gallery needs dim % 128 == 0, 128 <= dim <= 4096");
   if (!sim_topk_supported(dim)) throw std::invalid_argument("Gallery: dim needs dim % 32 == 0, 32 <= dim <= 4096");
   if (capacity < 1 || capacity > INT32_MAX) throw std::invalid_argument("Gallery: capacity outside 1..2^31 - 1");
   if (max_batch < 1) throw std::invalid_argument("Gallery: max_batch < 1");
@@ -16,17 +19,20 @@ Gallery::Gallery(int dim, long capacity, int device, bool cosine, int max_batch)
   DMLC_HIP_CHECK(hipGetDeviceProperties(&prop, device_));
   num_cus_ = prop.multiProcessorCount;
   // the widest launch a search can make: the slice count never exceeds the CU count
-  ws_bytes_ = sim_topk_ws_bytes(max_batch_, kMaxTopK, sim_topk_slices(max_batch_, capacity_, num_cus_));
+  const int slices = sim_topk_slices(max_batch_, capacity_, num_cus_);
+  ws_bytes_ = e4m3 ? sim_topk8_ws_bytes(max_batch_, kMaxTopK, slices) : sim_topk_ws_bytes(max_batch_, kMaxTopK, slices);
   removed_.assign((size_t)(capacity_ + 63) / 64, 0);
   try {
-    DMLC_HIP_CHECK(hipMalloc(&rows_, (size_t)capacity_ * dim_ * 2));
+    DMLC_HIP_CHECK(hipMalloc(&rows_, (size_t)capacity_ * dim_ * (e4m3 ? 1 : 2)));
     DMLC_HIP_CHECK(hipMalloc(&ws_, ws_bytes_));
     DMLC_HIP_CHECK(hipMalloc(&labels_, (size_t)capacity_ * sizeof(int32_t)));
     DMLC_HIP_CHECK(hipMalloc(&cls_idx_, (size_t)max_batch_ * kMaxTopK * sizeof(int32_t)));
     DMLC_HIP_CHECK(hipMalloc(&cls_score_, (size_t)max_batch_ * kMaxTopK * sizeof(float)));
     DMLC_HIP_CHECK(hipMalloc(&ids_dev_, (size_t)kIdsChunk * sizeof(int32_t)));
     DMLC_HIP_CHECK(hipHostMalloc(&ids_host_, (size_t)kIdsChunk * sizeof(int32_t), hipHostMallocDefault));
-    if (cosine_) {
+    if (e4m3) {  // (the queries' codes and scales live in the workspace)
+      DMLC_HIP_CHECK(hipMalloc(&inv_norm_, (size_t)capacity_ * sizeof(float)));
+    } else if (cosine_) {
       DMLC_HIP_CHECK(hipMalloc(&inv_norm_, (size_t)capacity_ * sizeof(float)));
       DMLC_HIP_CHECK(hipMalloc(&qpack_, (size_t)max_batch_ * dim_ * 2));
       DMLC_HIP_CHECK(hipMalloc(&q_scale_, (size_t)max_batch_ * sizeof(float)));
@@ -62,7 +68,10 @@ long Gallery::add(const float* rows_dev, int M, const int32_t* labels_dev, hipSt
   const long first = size_;
   if (M == 0) return first;
   DMLC_HIP_CHECK(hipSetDevice(device_));
-  gallery_pack(rows_dev, (char*)rows_ + (size_t)first * dim_ * 2, cosine_ ? inv_norm_ + first : nullptr, M, dim_, s);
+  if (dtype_ == GalleryDType::E4M3)
+    gallery_pack8(rows_dev, TensorDType::F32, (char*)rows_ + (size_t)first * dim_, inv_norm_ + first, cosine_, M, dim_, s);
+  else
+    gallery_pack(rows_dev, (char*)rows_ + (size_t)first * dim_ * 2, cosine_ ? inv_norm_ + first : nullptr, M, dim_, s);
   if (labels_dev)
     DMLC_HIP_CHECK(hipMemcpyAsync(labels_ + first, labels_dev, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   else
@@ -115,6 +124,13 @@ void Gallery::search(const void* q, TensorDType qdt, int B, int k, int32_t* idx,
     throw std::invalid_argument("Gallery::search: queries are fp32 or bf16");
   if (B == 0) return;
   DMLC_HIP_CHECK(hipSetDevice(device_));
+  // the row filter only where it can change the answer: every label is >= 0 until a row is removed
+  const bool filter = removed_count_ > 0 || q_want;
+  if (dtype_ == GalleryDType::E4M3) {
+    sim_topk8(q, qdt, rows_, inv_norm_, cosine_, B, size_, dim_, k, idx, score, ws_, ws_bytes_, num_cus_, s, 0,
+              filter ? labels_ : nullptr, q_want);
+    return;
+  }
   const float* q_scale = nullptr;
   if (cosine_) {  // the queries' inverse norms, of their bf16-rounded values
     if (qdt == TensorDType::F32) {
@@ -126,8 +142,6 @@ void Gallery::search(const void* q, TensorDType qdt, int B, int k, int32_t* idx,
     }
     q_scale = q_scale_;
   }
-  // the row filter only where it can change the answer: every label is >= 0 until a row is removed
-  const bool filter = removed_count_ > 0 || q_want;
   sim_topk(q, qdt, q_scale, rows_, cosine_ ? inv_norm_ : nullptr, B, size_, dim_, k, idx, score, ws_, ws_bytes_,
            num_cus_, s, 0, filter ? labels_ : nullptr, q_want);
 }

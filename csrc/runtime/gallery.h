@@ -9,6 +9,12 @@
 // a removed row's label is -1, which the kernel's row filter reads: a search
 // can be restricted to live rows of one label per query, and classify() is
 // the search followed by the k-NN vote (csrc/kernels/knn_vote.hip).
+//
+// Storage is bf16 (the default) or e4m3: one byte per element and one fp32
+// scale per row under either metric (kernels.h, sim_topk8's quantisation
+// rule), searched on the block-scaled fp8 MFMA: half the bytes per row and
+// half the MFMA cycles, for the rounding of a 3-bit mantissa. Everything
+// below holds for both; "bf16-rounded" reads "quantised" for e4m3.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,13 +25,17 @@
 
 namespace dmlc {
 
+enum class GalleryDType { BF16, E4M3 };
+
 class Gallery {
  public:
   // Everything is allocated here, sized for max_batch queries and kMaxTopK:
   // bf16 rows [capacity, dim], inverse norms and labels [capacity], the
   // search and classify workspace, the staging of remove(). dim:
-  // sim_topk_supported.
-  Gallery(int dim, long capacity, int device, bool cosine, int max_batch = 256);
+  // sim_topk_supported. E4M3: codes [capacity, dim] of one byte, scales
+  // [capacity] under both metrics; dim: sim_topk8_supported.
+  Gallery(int dim, long capacity, int device, bool cosine, int max_batch = 256,
+          GalleryDType dtype = GalleryDType::BF16);
   ~Gallery();
   Gallery(const Gallery&) = delete;
   Gallery& operator=(const Gallery&) = delete;
@@ -34,6 +44,7 @@ class Gallery {
   long capacity() const { return capacity_; }
   int device() const { return device_; }
   bool cosine() const { return cosine_; }
+  GalleryDType dtype() const { return dtype_; }
   int max_batch() const { return max_batch_; }
   long size() const { return size_; }          // rows ever added since clear(), removed ones included
   long live() const { return size_ - removed_count_; }
@@ -74,8 +85,9 @@ class Gallery {
   int dim_, device_, max_batch_, num_cus_ = 0;
   long capacity_, size_ = 0;
   bool cosine_;
-  void* rows_ = nullptr;        // bf16 [capacity, dim]
-  float* inv_norm_ = nullptr;   // [capacity] (cosine)
+  GalleryDType dtype_;
+  void* rows_ = nullptr;        // bf16 or e4m3 [capacity, dim]
+  float* inv_norm_ = nullptr;   // [capacity] (cosine; e4m3: the rows' scales under either metric)
   void* qpack_ = nullptr;       // bf16 [max_batch, dim] (cosine, fp32 queries)
   float* q_scale_ = nullptr;    // [max_batch] (cosine)
   void* ws_ = nullptr;

@@ -20,15 +20,28 @@ class Gallery:
     metric "dot": score = the dot product of the bf16-rounded query and row;
     "cosine": that divided by both L2 norms (of the rounded vectors, each
     clamped at 1e-12 as ``F.normalize`` does). All device memory, the search
-    workspace for ``max_batch`` queries included, is allocated here."""
+    workspace for ``max_batch`` queries included, is allocated here.
 
-    def __init__(self, dim: int, capacity: int, device: int = 0, metric: str = "cosine", max_batch: int = 256):
+    dtype "e4m3": rows are stored as one-byte OCP e4m3 codes with one fp32
+    scale per row (dim % 128 == 0, 128 <= dim <= 4096) and searched on the
+    block-scaled fp8 MFMA: half the bytes, half the MFMA cycles. A row (and
+    each query) is multiplied by the largest power of two that keeps its
+    largest magnitude <= 448 and rounded to e4m3 (``ops.gallery_pack8``);
+    "dot" is then the dot product of the dequantised vectors, "cosine" that
+    of the codes divided by both L2 norms of the codes. Every method behaves
+    as on a bf16 gallery."""
+
+    def __init__(self, dim: int, capacity: int, device: int = 0, metric: str = "cosine", max_batch: int = 256,
+                 dtype: str = "bf16"):
         require_gpu()
         if metric not in ("cosine", "dot"):
             raise ValueError(f"metric is 'cosine' or 'dot', got {metric!r}")
+        if dtype not in ("bf16", "e4m3"):
+            raise ValueError(f"dtype is 'bf16' or 'e4m3', got {dtype!r}")
         self.device = torch.device("cuda", device)
-        self._g = native().Gallery(dim, capacity, device, metric, max_batch)
+        self._g = native().Gallery(dim, capacity, device, metric, max_batch, dtype)
         self.dim, self.capacity, self.metric, self.max_batch = dim, capacity, metric, max_batch
+        self.dtype = dtype
         self.max_topk = native().MAX_TOPK
 
     def __len__(self) -> int:

@@ -1012,32 +1012,99 @@ def sim_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, q_scale: torc
     N, D = gallery.shape
     if not C.sim_topk_supported(D):
         raise ValueError(f"sim_topk: needs D % 32 == 0 and 32 <= D <= 4096, got D = {D}")
-    qdt = query_rows(queries, D, dev, "sim_topk")
-    B = queries.shape[0]
-    if not isinstance(k, int) or not 1 <= k <= min(N, C.MAX_TOPK):
-        raise ValueError(f"sim_topk: k = {k} outside 1..min(N = {N}, {C.MAX_TOPK})")
-    for t, n, what in ((q_scale, B, "q_scale"), (g_scale, N, "g_scale")):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (n,) or t.device != dev
-                              or not t.is_contiguous()):
-            raise ValueError(f"sim_topk: {what} must be contiguous float32 [{n}] on {dev}")
-    if q_want is not None and g_label is None:
-        raise ValueError("sim_topk: q_want needs g_label")
-    for t, n, what in ((g_label, N, "g_label"), (q_want, B, "q_want")):
-        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (n,) or t.device != dev
-                              or not t.is_contiguous()):
-            raise ValueError(f"sim_topk: {what} must be contiguous int32 [{n}] on {dev}")
-    cus = torch.cuda.get_device_properties(dev).multi_processor_count
-    if slices is None:
-        slices = C.sim_topk_slices(B, N, cus)
-    elif not isinstance(slices, int) or not 1 <= slices <= C.sim_topk_max_slices(N):
-        raise ValueError(f"sim_topk: slices = {slices} outside 1..{C.sim_topk_max_slices(N)}")
-    idx, score = topk_out(out, B, k, dev, "sim_topk")
+    qdt, B, slices, cus, idx, score = _sim_args("sim_topk", queries, N, D, dev, k, q_scale, g_scale, out, slices,
+                                                g_label, q_want)
     if B == 0:
         return idx, score
     ws = _sim_ws(dev, C.sim_topk_ws_bytes(B, k, slices))
     C.sim_topk(_ptr(queries), qdt, _ptr(q_scale), _ptr(gallery), _ptr(g_scale), B, N, D, k, _ptr(idx), _ptr(score),
                _ptr(ws), ws.numel(), cus, _stream(), slices=slices, g_label=_ptr(g_label), q_want=_ptr(q_want))
     return idx, score
+
+
+def _sim_args(what, queries, N, D, dev, k, q_scale, g_scale, out, slices, g_label, q_want):
+    """The checks sim_topk and sim_topk8 share, once the gallery's own are done:
+    (query dtype, B, slices, CUs, idx, score)."""
+    C = native()
+    qdt = query_rows(queries, D, dev, what)
+    B = queries.shape[0]
+    if not isinstance(k, int) or not 1 <= k <= min(N, C.MAX_TOPK):
+        raise ValueError(f"{what}: k = {k} outside 1..min(N = {N}, {C.MAX_TOPK})")
+    for t, n, name in ((q_scale, B, "q_scale"), (g_scale, N, "g_scale")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (n,) or t.device != dev
+                              or not t.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be contiguous float32 [{n}] on {dev}")
+    if q_want is not None and g_label is None:
+        raise ValueError(f"{what}: q_want needs g_label")
+    for t, n, name in ((g_label, N, "g_label"), (q_want, B, "q_want")):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (n,) or t.device != dev
+                              or not t.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be contiguous int32 [{n}] on {dev}")
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    if slices is None:
+        slices = C.sim_topk_slices(B, N, cus)
+    elif not isinstance(slices, int) or not 1 <= slices <= C.sim_topk_max_slices(N):
+        raise ValueError(f"{what}: slices = {slices} outside 1..{C.sim_topk_max_slices(N)}")
+    idx, score = topk_out(out, B, k, dev, what)
+    return qdt, B, slices, cus, idx, score
+
+
+def sim_topk8(queries: torch.Tensor, gallery: torch.Tensor, g_scale: torch.Tensor, k: int, metric: str = "cosine",
+              out=None, slices: int | None = None, g_label: torch.Tensor | None = None,
+              q_want: torch.Tensor | None = None):
+    """``sim_topk`` over an e4m3 gallery on the block-scaled fp8 MFMA.
+    gallery: float8_e4m3fn codes [N,D] and g_scale float32 [N], as
+    ``gallery_pack8(rows, metric)`` returns them; D % 128 == 0, 128 <= D <=
+    4096. queries: float32 or bfloat16 [B,D], quantised by the same rule on
+    the way in. score(b, n) = ((sum_d cq[b,d] cg[n,d]) q_scale[b]) g_scale[n]:
+    "dot": the dot product of the dequantised vectors; "cosine": the codes'
+    cosine. k, ``out``, ``slices``, ``g_label`` and ``q_want`` as for
+    ``sim_topk``; the answer's bits do not depend on the slice count."""
+    _need_cuda(queries, gallery, g_scale, g_label, q_want)
+    C = native()
+    dev = gallery.device
+    if metric not in ("cosine", "dot"):
+        raise ValueError(f"sim_topk8: metric is 'cosine' or 'dot', got {metric!r}")
+    if gallery.dtype != torch.float8_e4m3fn or gallery.dim() != 2 or not gallery.is_contiguous():
+        raise ValueError(f"sim_topk8: gallery must be contiguous float8_e4m3fn [N,D], got {gallery.dtype} "
+                         f"{tuple(gallery.shape)}")
+    N, D = gallery.shape
+    if not C.sim_topk8_supported(D):
+        raise ValueError(f"sim_topk8: needs D % 128 == 0 and 128 <= D <= 4096, got D = {D}")
+    if g_scale is None:
+        raise ValueError("sim_topk8: an e4m3 gallery needs its g_scale")
+    qdt, B, slices, cus, idx, score = _sim_args("sim_topk8", queries, N, D, dev, k, None, g_scale, out, slices,
+                                                g_label, q_want)
+    if B == 0:
+        return idx, score
+    ws = _sim_ws(dev, C.sim_topk8_ws_bytes(B, k, slices))
+    C.sim_topk8(_ptr(queries), qdt, _ptr(gallery), _ptr(g_scale), metric == "cosine", B, N, D, k, _ptr(idx),
+                _ptr(score), _ptr(ws), ws.numel(), cus, _stream(), slices=slices, g_label=_ptr(g_label),
+                q_want=_ptr(q_want))
+    return idx, score
+
+
+def gallery_pack8(rows: torch.Tensor, metric: str = "cosine"):
+    """float32 or bfloat16 rows [M,D] -> (codes float8_e4m3fn [M,D], scale
+    float32 [M]), as an e4m3 gallery stores them. Per row: amax = max |v|, e
+    the largest integer with amax 2^e <= 448 (clamped to +-126; 0 for a zero
+    row), codes = e4m3(v 2^e) to nearest even; scale = 2^-e ("dot") or 1 /
+    max(sqrt(sum codes^2), 1e-12) ("cosine"). D % 128 == 0, 128 <= D <= 4096."""
+    _need_cuda(rows)
+    if metric not in ("cosine", "dot"):
+        raise ValueError(f"gallery_pack8: metric is 'cosine' or 'dot', got {metric!r}")
+    if rows.dtype not in (torch.float32, torch.bfloat16) or rows.dim() != 2 or not rows.is_contiguous():
+        raise ValueError(f"gallery_pack8 expects contiguous float32 / bfloat16 [M,D], got {rows.dtype} "
+                         f"{tuple(rows.shape)}")
+    M, D = rows.shape
+    C = native()
+    if not C.sim_topk8_supported(D):
+        raise ValueError(f"gallery_pack8: needs D % 128 == 0 and 128 <= D <= 4096, got D = {D}")
+    codes = torch.empty(M, D, dtype=torch.float8_e4m3fn, device=rows.device)
+    scale = torch.empty(M, dtype=torch.float32, device=rows.device)
+    C.gallery_pack8(_ptr(rows), getattr(C.TensorDType, _TENSOR_DTYPES[rows.dtype]), _ptr(codes), _ptr(scale),
+                    metric == "cosine", M, D, _stream())
+    return codes, scale
 
 
 def knn_vote(idx: torch.Tensor, score: torch.Tensor, g_label: torch.Tensor, weighted: bool = False, out=None):

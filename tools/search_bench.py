@@ -25,7 +25,19 @@ dmlc.Gallery, InferenceEngine.search), written as plain text. One GPU.
           knn_vote launch at B = 256, and a graph-replayed ResNet18 b256
           classify_knn() next to search(), both at k = 5.
 
-usage: python tools/search_bench.py [kernel] [engine] [filtered] [--blocks 5] [--base-lib LIB]
+  e4m3    the e4m3 gallery (profiles/search_e4m3.txt) at D = 512: the bf16
+          launch and the e4m3 launch (its quantising of the queries
+          included) interleaved at (B, N, k) = (256, 1 M, 1), (256, 1 M, 16),
+          (1, 1 M, 1), (256, 100 k, 1), both metrics, with the e4m3 filtered
+          form on live rows and, with --base-lib, the bf16 launch of the
+          build to compare with measured twice (its two medians' difference
+          is the box's spread, the bar for "the bf16 launch did not move").
+          Then a gallery_pack8 launch at M = 256, a graph-replayed ResNet18
+          b256 search() against a 100 k gallery of each dtype, and the e4m3
+          gallery's recall@1 / recall@16 of the bf16 gallery's answer on
+          randn and on a calibrated ResNet18's embeddings of mixed_images.
+
+usage: python tools/search_bench.py [kernel] [engine] [filtered] [e4m3] [--blocks 5] [--base-lib LIB]
                                     [--out profiles/search.txt]
 """
 import argparse
@@ -143,19 +155,25 @@ def bench_engine(a, emit):
     emit(f"  added by the search     {ms - me:9.1f} us = {(ms - me) / me * 100:.1f} % of the forward")
 
 
-# dmlc::sim_topk as it was before the row filter's two trailing arguments
+# dmlc::sim_topk as it was before the row filter's two trailing arguments, and with them
 _BASE_SYMBOL = "_ZN4dmlc8sim_topkEPKvNS_11TensorDTypeEPKfS1_S4_iliiPiPfPvmiP12ihipStream_ti"
+_BASE_SYMBOL_FILTER = _BASE_SYMBOL + "PKiSB_"
 
 
 def _base_sim_topk(path):
     """The unfiltered launcher of another build of the library, or None."""
     if not path:
         return None
-    fn = getattr(ctypes.CDLL(os.path.abspath(path), mode=ctypes.RTLD_LOCAL), _BASE_SYMBOL)
+    lib = ctypes.CDLL(os.path.abspath(path), mode=ctypes.RTLD_LOCAL)
     vp = ctypes.c_void_p
-    fn.argtypes = [vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int, vp, vp, vp,
-                   ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_int]
-    fn.restype = None
+    args = [vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int, vp, vp, vp,
+            ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_int]
+    if hasattr(lib, _BASE_SYMBOL_FILTER):
+        fn = getattr(lib, _BASE_SYMBOL_FILTER)
+        fn.argtypes, fn.restype = args + [vp, vp], None
+        return lambda *a: fn(*a, None, None)
+    fn = getattr(lib, _BASE_SYMBOL)
+    fn.argtypes, fn.restype = args, None
     return fn
 
 
@@ -258,9 +276,143 @@ def bench_filtered(a, emit):
         emit(f"  {name + '()':<15} {_fmt(t[name])} per batch  {B / statistics.median(t[name]) * 1e6:9.0f} images/s")
 
 
+def _recall(got, want):
+    """(recall@1, recall@k) of idx `got` [B, k] against `want` [B, k]."""
+    r1 = (got[:, 0] == want[:, 0]).float().mean().item()
+    rk = (got[:, :, None] == want[:, None, :]).any(-1).float().mean().item()
+    return r1, rk
+
+
+def bench_e4m3(a, emit):
+    dev = torch.device("cuda", 0)
+    C = dmlc.native()
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    stream = torch.cuda.current_stream().cuda_stream
+    base = _base_sim_topk(a.base_lib)
+    D, BF = 512, C.TensorDType.BF16
+    emit(f"e4m3 gallery ({torch.cuda.get_device_name(0)}, {cus} CUs), D = {D}, randn, native launchers on preallocated "
+         f"outputs, bf16 queries; the e4m3 launch includes quantising its queries (gallery_pack8, one more launch); "
+         f"device events around back-to-back launches, median (min - max) of {a.blocks} interleaved blocks. base / "
+         f"base again: the bf16 launch of the build to compare with "
+         f"({'given' if base else 'not given: --base-lib'}), twice in the same turns: their difference is the box's "
+         f"spread. e4m3 live: the filtered form, every row live. TB/s = the gallery's bytes / time:")
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for N, shapes in ((1_000_000, ((256, 1), (256, 16), (1, 1))), (100_000, ((256, 1),))):
+        g32 = torch.randn(N, D, device=dev, generator=gen)
+        g, ginv = ops.gallery_pack(g32, with_norms=True)
+        packed = {m: ops.gallery_pack8(g32, m) for m in ("dot", "cosine")}
+        del g32
+        live = torch.zeros(N, dtype=torch.int32, device=dev)
+        for B, k in shapes:
+            qb, qinv = ops.gallery_pack(torch.randn(B, D, device=dev, generator=gen), with_norms=True)
+            slices = C.sim_topk_slices(B, N, cus)
+            ws = torch.empty(max(C.sim_topk_ws_bytes(B, k, slices), C.sim_topk8_ws_bytes(B, k, slices)),
+                             dtype=torch.uint8, device=dev)
+            idx = torch.empty(B, k, dtype=torch.int32, device=dev)
+            score = torch.empty(B, k, dtype=torch.float32, device=dev)
+            for metric in ("dot", "cosine"):
+                qs, gs = (qinv.data_ptr(), ginv.data_ptr()) if metric == "cosine" else (0, 0)
+                codes, scale = packed[metric]
+
+                def run16():
+                    C.sim_topk(qb.data_ptr(), BF, qs, g.data_ptr(), gs, B, N, D, k, idx.data_ptr(), score.data_ptr(),
+                               ws.data_ptr(), ws.numel(), cus, stream)
+
+                def run_base():
+                    base(qb.data_ptr(), int(BF), qs or None, g.data_ptr(), gs or None, B, N, D, k, idx.data_ptr(),
+                         score.data_ptr(), ws.data_ptr(), ws.numel(), cus, stream, 0)
+
+                def run8(label=None):
+                    C.sim_topk8(qb.data_ptr(), BF, codes.data_ptr(), scale.data_ptr(), metric == "cosine", B, N, D, k,
+                                idx.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(), cus, stream,
+                                g_label=0 if label is None else label.data_ptr())
+                fns = {}
+                run16()
+                torch.cuda.synchronize()
+                want = idx.clone()
+                if base:
+                    mine = score.clone()
+                    run_base()
+                    torch.cuda.synchronize()
+                    if not (torch.equal(want, idx) and torch.equal(mine, score)):
+                        raise SystemExit("search_bench: the bf16 launch and the base build's differ in bits")
+                    fns["base"] = run_base
+                fns["bf16"] = run16
+                fns["e4m3"] = run8
+                if base:
+                    fns["base again"] = run_base
+                fns["e4m3 live"] = lambda: run8(live)
+                run8()
+                torch.cuda.synchronize()
+                r1, rk = _recall(idx, want)
+                t = _interleaved(fns, a.blocks)
+                ref = statistics.median(t["bf16"])
+                for name in fns:
+                    m = statistics.median(t[name])
+                    nbytes = N * D * (1 if name.startswith("e4m3") else 2)
+                    emit(f"  N={N:<8} B={B:<4} k={k:<3} {metric:<6} {name:<10} {_fmt(t[name])}  {m / ref:6.3f} x bf16  "
+                         f"{nbytes / m / 1e6:6.3f} TB/s  {2.0 * B * N * D / m / 1e6:7.1f} TF/s  slices {slices}")
+                emit(f"  {'':<28} e4m3 against the bf16 answer: recall@1 {r1:.3f}" + (f", recall@{k} {rk:.3f}" if k > 1 else ""))
+                if base:
+                    b1, b2 = statistics.median(t["base"]), statistics.median(t["base again"])
+                    emit(f"  {'':<28} spread of the base build: {abs(b1 - b2) / min(b1, b2) * 100:.2f} % between its two "
+                         f"medians; bf16 is {(ref / ((b1 + b2) / 2) - 1) * 100:+.2f} % off their mean")
+        del g, ginv, packed, live
+    # the quantiser alone
+    rows = torch.randn(256, D, device=dev, generator=gen)
+    codes = torch.empty(256, D, dtype=torch.uint8, device=dev)
+    scale = torch.empty(256, device=dev)
+    t = _interleaved({"pack8": lambda: C.gallery_pack8(rows.data_ptr(), C.TensorDType.F32, codes.data_ptr(),
+                                                       scale.data_ptr(), True, 256, D, stream)}, a.blocks)
+    emit(f"  gallery_pack8 M=256 D={D} fp32 rows, cosine   {_fmt(t['pack8'])} per launch (back to back)")
+    # recall at k = 16 on randn, cosine
+    N, B = 100_000, 256
+    g32 = torch.randn(N, D, device=dev, generator=gen)
+    q32 = torch.randn(B, D, device=dev, generator=gen)
+    gb, ginv = ops.gallery_pack(g32, with_norms=True)
+    qb, qinv = ops.gallery_pack(q32, with_norms=True)
+    want = ops.sim_topk(qb, gb, 16, qinv, ginv)[0]
+    got = ops.sim_topk8(q32, *ops.gallery_pack8(g32, "cosine"), 16, "cosine")[0]
+    r1, rk = _recall(got, want)
+    emit(f"  recall of the e4m3 gallery against the bf16 gallery's answer, cosine, k = 16, randn N={N} B={B}: "
+         f"recall@1 {r1:.3f}, recall@16 {rk:.3f}")
+    del g32, gb, ginv
+    # the engine
+    from dmlc.models import state_dict_f32
+    from dmlc.models.calibrated import calibrated, mixed_images
+    from dmlc.runtime import InferenceEngine
+    eng = InferenceEngine("resnet18", state_dict_f32(calibrated("resnet18", seed=11)), max_batch=B)
+    F = eng.feature_dim
+    gals = {dt: dmlc.Gallery(F, 2048, max_batch=B, dtype=dt) for dt in ("bf16", "e4m3")}
+    for i in range(8):
+        feats = eng.embed(mixed_images(B, seed=100 + i).to(dev))
+        for gal in gals.values():
+            gal.add(feats)
+    img = mixed_images(B, seed=1).to(dev)
+    want = eng.search(img, gals["bf16"], k=16)[0].clone()
+    got = eng.search(img, gals["e4m3"], k=16)[0].clone()
+    r1, rk = _recall(got, want)
+    emit(f"  the same on a calibrated resnet18's embeddings of mixed_images, 2048 stored images, {B} other queries: "
+         f"recall@1 {r1:.3f}, recall@16 {rk:.3f}")
+    gals = {dt: dmlc.Gallery(F, N, max_batch=B, dtype=dt) for dt in ("bf16", "e4m3")}
+    for i in range(0, N, 10_000):
+        rows = torch.randn(10_000, F, device=dev, generator=gen).abs()
+        for gal in gals.values():
+            gal.add(rows)
+    feats = torch.empty(B, F, device=dev)
+    out = (torch.empty(B, 16, dtype=torch.int32, device=dev), torch.empty(B, 16, device=dev))
+    fns = {"embed": lambda: eng.embed(img, out=feats),
+           "search bf16": lambda: eng.search(img, gals["bf16"], k=16, out=out),
+           "search e4m3": lambda: eng.search(img, gals["e4m3"], k=16, out=out)}
+    t = _interleaved(fns, a.blocks)
+    emit(f"engine, resnet18 b{B} graph replay, gallery of {N} x {F} (cosine, k = 16):")
+    for name in fns:
+        emit(f"  {name + '()':<15} {_fmt(t[name])} per batch  {B / statistics.median(t[name]) * 1e6:9.0f} images/s")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", nargs="*", default=["kernel", "engine"], help="kernel, engine, filtered")
+    ap.add_argument("what", nargs="*", default=["kernel", "engine"], help="kernel, engine, filtered, e4m3")
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--base-lib", default="", help="filtered: a library built from the commit to compare with")
     ap.add_argument("--out", default="")
@@ -280,6 +432,8 @@ def main():
             bench_engine(a, emit)
         elif w == "filtered":
             bench_filtered(a, emit)
+        elif w == "e4m3":
+            bench_e4m3(a, emit)
         else:
             raise SystemExit(f"unknown measurement: {w}")
     if a.out:
