@@ -153,7 +153,7 @@ struct Compute {
         }
       }
     }
-    w2rs = wave_rsrc(a.wf2 + (long)wn * kKS2 * 2 * 512, kKS2 * 2 * 1024);
+    w2rs = frag_rsrc(a.wf2, wn, 1, kKS2);
 #pragma unroll
     for (int ks = 0; ks < kPD - 1; ++ks)
 #pragma unroll

@@ -139,6 +139,18 @@ __device__ __forceinline__ int perm32(int n) {
   return 8 * (r >> 2) + 4 * nf + (r & 3);
 }
 
+// Input chunk swizzle of a pixel staged in LDS with key K (CPX 16-B chunks per
+// pixel): chunk c sits at physical chunk c ^ xswz(K). Pixels of >= 256 B fill
+// whole 64-bank windows; 128-B pixels take the window half of K's parity
+// (conv3x3_stream.hip's staging loop has the derivation).
+template <int CPX>
+__device__ __forceinline__ int xswz(int K) {
+  if constexpr (CPX >= 16)
+    return (K & 7) << 1;
+  else
+    return ((K >> 1) & 3) << 1;
+}
+
 // ---- waits and barriers
 //
 // For the memory operations the compiler does not track (the LDS-DMA and
@@ -235,6 +247,23 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t wave_rsrc(const void* p, int b
   const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
   return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0,
                                            __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+
+// Weights in fragment order, [CO/32][KT][2][64 lanes][8]: the device-side
+// inverse of stream_frag_index (kernels.h). frag_rsrc: the descriptor over
+// `groups` consecutive 32-channel groups from `group` on (KT K steps each);
+// frag_load: this lane's 8 weights of N fragment nf (group nf / 2 of the
+// descriptor) of K step t, the fragment offset a scalar.
+// Used by conv_direct.hip; bottleneck56.hip takes the descriptor. The register-
+// weight paths of conv3x3_stream, conv3x3_rows and conv3x3_block spell the
+// same two expressions out on purpose: through the helpers their register
+// allocation changed (profiles/conv_direct.txt).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t frag_rsrc(const bf16* wf, int group, int groups, int KT) {
+  return wave_rsrc(wf + (long)group * KT * 2 * 512, groups * KT * 2 * 1024);
+}
+__device__ __forceinline__ bf16x8 frag_load(__amdgpu_buffer_rsrc_t rs, int lane, int KT, int t, int nf) {
+  return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+                                        rs, lane * 16, ((nf >> 1) * KT * 2 + t * 2 + (nf & 1)) * 1024, 0));
 }
 
 // ---- wave reductions

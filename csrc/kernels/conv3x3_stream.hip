@@ -87,15 +87,6 @@ struct alignas(8) u32x2s {
 // reads chunk fq of row 16nf + fr).
 __device__ __forceinline__ int wswz(int n, int c) { return c ^ (3 * ((n >> 2) & 1)); }
 
-// Input chunk swizzle of a staged pixel with key K (see the staging loop).
-template <int CPX>
-__device__ __forceinline__ int xswz(int K) {
-  if constexpr (CPX >= 16)
-    return (K & 7) << 1;
-  else
-    return ((K >> 1) & 3) << 1;
-}
-
 // Geometry shared by the kernel and its launcher: output H x W, stride S, a
 // workgroup owns HS output rows of one image (PARTS = H / HS > 1) or IMG whole
 // images (PARTS == 1).

@@ -20,6 +20,12 @@ namespace dmlc {
                                " at " + __FILE__ + ":" + std::to_string(__LINE__)); \
   } while (0)
 
+// Do the byte ranges [a, a + na) and [b, b + nb) share a byte? (launchers of
+// kernels that cannot run in place)
+inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+}
+
 // Implicit-GEMM convolution (also used for fully-connected layers as a 1x1
 // conv on a [B,1,1,C] tensor).
 //   x    : bf16 NHWC [B, H, W, Cin], Cin % 64 == 0; or, with `stem`, the
@@ -226,7 +232,7 @@ bool conv3x3_block_supported(int H, int W, int C);
 void conv3x3_block(const void* x, const void* wf1, const float* bias1, const void* wf2, const float* bias2, void* y,
                    const void* zero, int B, hipStream_t s);
 // Direct 3x3/s1/p1 conv on 13x13 images, the whole image in LDS
-// (conv3x3_13.hip): AlexNet features.6/.8/.10 (192->384, 384->256,
+// (conv_direct.hip): AlexNet features.6/.8/.10 (192->384, 384->256,
 // 256->256). wf: fragment-order weights (stream_frag_index, K = 9 Cin).
 bool conv3x3_13_supported(int H, int W, int Cin, int Cout);
 // ypool: also fuse the following 3x3/s2 max-pool (13 -> 6), written instead of
@@ -235,7 +241,7 @@ bool conv3x3_13_pool_supported(int Cin, int Cout);
 void conv3x3_13(const void* x, const void* wf, const float* bias, void* y, const void* zero, int B, int Cin, int Cout,
                 bool relu, hipStream_t s, void* ypool = nullptr);
 // Direct 5x5/s1/p2 conv 27x27x64 -> 192 with the image in LDS
-// (conv5x5_27.hip): AlexNet features.3. wf: fragment-order weights
+// (conv_direct.hip): AlexNet features.3. wf: fragment-order weights
 // (stream_frag_index, K = 1600); bias + ReLU.
 bool conv5x5_27_supported(int H, int W, int Cin, int Cout, int pad);
 // ypool: also fuse the following 3x3/s2 max-pool (27 -> 13), written instead of y.

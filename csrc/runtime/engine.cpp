@@ -587,7 +587,7 @@ void Engine::layout_weights() {
     }
     if (L.plain() && L.kh == 5 && L.kw == 5 && L.stride == 1 &&
         conv5x5_27_supported(is.H, is.W, is.C, L.cout, L.pad)) {
-      L.wf_off = off;  // fragment-order copy for conv5x5_27.hip
+      L.wf_off = off;  // fragment-order copy for conv_direct.hip
       L.wf_bytes = (size_t)L.cout * L.kpad * 2;
       off = align_up(off + L.wf_bytes, 256);
     }

@@ -127,8 +127,8 @@ struct EngineOptions {
   bool chain_1x1 = true;
   bool fused_pool = true;        // the last conv's epilogue computes the global average pool
   bool fused_head = true;        // avgpool + fc + softmax / top-1 in one kernel (head.hip)
-  bool direct13 = true;          // AlexNet's 13x13 3x3 convs with the image resident in LDS (conv3x3_13.hip)
-  bool direct27 = true;          // AlexNet's 5x5 conv on 27x27x64 the same way (conv5x5_27.hip)
+  bool direct13 = true;          // AlexNet's 13x13 3x3 convs with the image resident in LDS (conv_direct.hip)
+  bool direct27 = true;          // AlexNet's 5x5 conv on 27x27x64 the same way (conv_direct.hip)
   bool fc_small = true;          // weight-streaming GEMV for fc layers at B <= 16 (fc_small.hip)
   // downsample convs on a side stream: measured slower (the branch slows its
   // sibling conv1 by 10-12 us and adds ~10 us of fork/join gaps per block:

@@ -750,7 +750,7 @@ def alex_stem(images: torch.Tensor, w: torch.Tensor, bias: torch.Tensor) -> torc
 
 
 def conv5x5_27(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, pool: bool = False) -> torch.Tensor:
-    """AlexNet features.3 (conv5x5_27.hip): relu(conv 5x5/s1/p2 + bias) on bf16
+    """AlexNet features.3 (conv_direct.hip): relu(conv 5x5/s1/p2 + bias) on bf16
     [B, 27, 27, 64] -> [B, 27, 27, 192]; with ``pool`` the following 3x3/s2
     max-pool is fused and [B, 13, 13, 192] returned instead. w_packed: conv2d
     packed weights [>= 192, 1600]."""
@@ -769,7 +769,7 @@ def conv5x5_27(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, pool
 
 
 def conv3x3_13(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, relu: bool, pool: bool = False) -> torch.Tensor:
-    """AlexNet features.6 / .8 / .10 (conv3x3_13.hip): relu?(conv 3x3/s1/p1 +
+    """AlexNet features.6 / .8 / .10 (conv_direct.hip): relu?(conv 3x3/s1/p1 +
     bias) on bf16 [B, 13, 13, Cin] for (Cin, Cout) = (192, 384), (384, 256),
     (256, 256). With ``pool`` (256 -> 256 with ReLU only) the following 3x3/s2
     max-pool is fused and [B, 6, 6, 256] returned instead. w_packed: conv2d

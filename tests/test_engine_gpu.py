@@ -479,7 +479,7 @@ def test_alexnet_small_batch_fc_matches_reference(gpu, B):
 @pytest.mark.parametrize("B", [5, 256])
 def test_alexnet_direct13_matches_igemm(gpu, B):
     """AlexNet's 13x13 convs (features.6/.8/.10) and its 5x5 conv (features.3)
-    on the LDS-resident direct convs (conv3x3_13.hip, conv5x5_27.hip) vs the
+    on the LDS-resident direct convs (conv_direct.hip) vs the
     implicit GEMM (direct13 / direct27 off): both bf16 MFMA
     with fp32 accumulation, different K order, so logits agree to bf16
     rounding; and vs fp32 torch.nn on a few images. The direct kernel is the

@@ -161,6 +161,39 @@ def test_conv3x3_13_bad_shapes(gpu):
         ops.conv5x5_27(x, wp, b)
 
 
+def test_direct_conv_bad_operands(gpu):
+    """The launchers refuse a bias they cannot read as float4 and an output
+    that overlaps the input (another workgroup's image would be overwritten
+    while it is staged). Every operand is a view into an allocation large
+    enough for a launch that wrongly went ahead."""
+    C = ops.native()
+    zero, s = ops._ptr(ops._zero_page(torch.device(gpu))), ops._stream()
+    bias = torch.zeros(256 + 8, device=gpu)
+    # 13x13, 256 -> 256: x and y have the same size
+    x13 = torch.zeros(1, 13, 13, 256, dtype=torch.bfloat16, device=gpu)
+    wp13 = torch.zeros(256, 9 * 256, dtype=torch.bfloat16, device=gpu)
+    with pytest.raises(ValueError):
+        ops.conv3x3_13(x13, wp13, bias[1:257], relu=True)
+    wf13 = ops.stream_weight_frag(wp13, 256)
+    y13 = torch.empty_like(x13)
+    for relu, ypool in ((True, 0), (True, ops._ptr(x13))):
+        with pytest.raises(ValueError):
+            C.conv3x3_13(ops._ptr(x13), ops._ptr(wf13), ops._ptr(bias), ops._ptr(x13) if not ypool else ops._ptr(y13),
+                         zero, 1, 256, 256, relu, s, ypool)
+    # 27x27, 64 -> 192: x is the head of an allocation of y's size
+    buf = torch.zeros(1, 27, 27, 192, dtype=torch.bfloat16, device=gpu)
+    x27 = buf.view(-1)[:27 * 27 * 64].view(1, 27, 27, 64)
+    wp27 = torch.zeros(192, 1600, dtype=torch.bfloat16, device=gpu)
+    with pytest.raises(ValueError):
+        ops.conv5x5_27(x27, wp27, bias[1:193])
+    wf27 = ops.stream_weight_frag(wp27, 192)
+    with pytest.raises(ValueError):
+        C.conv5x5_27(ops._ptr(x27), ops._ptr(wf27), ops._ptr(bias), ops._ptr(buf), zero, 1, s, 0)
+    with pytest.raises(ValueError):
+        C.conv5x5_27(ops._ptr(x27), ops._ptr(wf27), ops._ptr(bias), 0, zero, 1, s, ops._ptr(buf))
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("B", [1, 2])
 def test_conv5x5_27(gpu, B):
     x, w, bias = _conv_operands(B, 64, 192, 27, 5, seed=40 + B)

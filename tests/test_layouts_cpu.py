@@ -907,3 +907,147 @@ def test_igemm_fragment_reads_conflict_free(in8):
                 r = base + fr
                 addr.append(r * 128 + ((rd(fq) ^ h(r)) << 4))
             assert _b128_ways(addr) == 1, (base, in8)
+
+
+# conv_direct.hip: the whole image in LDS. (H, W, KS, PAD, CI,
+# waves, pixel fragments per wave when the waves split them, pool tile chunks
+# per pixel / tiles / tile base relative to the staged image's end; 0 chunks =
+# no fused pool), and `ways`: the worst ds_read_b128 conflict degree over every
+# operand read, computed here from the kernels' formulas and pinned (see the
+# test; reads whose 64 lanes are all in the image are conflict free everywhere).
+# (384->256 has the per-wave pool form in its trait, so it is modelled, though the
+# launcher offers the fused pool for 256->256 only.)
+_DIRECT = {
+    "13x13 192->384": dict(H=13, KS=3, PAD=1, CI=192, waves=4, fpw=None, NC=0, tiles=0, ways=1),
+    "13x13 384->256": dict(H=13, KS=3, PAD=1, CI=384, waves=4, fpw=None, NC=8, tiles=4, ways=1),
+    "13x13 256->256": dict(H=13, KS=3, PAD=1, CI=256, waves=4, fpw=None, NC=8, tiles=4, ways=1),
+    "27x27 64->192": dict(H=27, KS=5, PAD=2, CI=64, waves=8, fpw=6, NC=4, tiles=1, ways=2),
+}
+
+
+@pytest.mark.parametrize("name", list(_DIRECT))
+def test_direct_conv_lds_layout(name):
+    """The image-in-LDS direct convs, modelled from their shapes' numbers.
+
+    Staging: physical 16-B slot ps = K * PXC + pc holds logical chunk
+    pc ^ xswz(K) of pixel K (or padding from the zero page); every real chunk
+    lands exactly once, DMA instruction i fills the 64 consecutive slots at
+    1024 i, the zero pixel follows the image.
+    Operand reads xa[f] + (tsw ^ 64 cc), for every tap, pixel fragment, K step
+    in a tap and lane: a real pixel's in-image tap reads the staged place of
+    chunk 4 cc + g of pixel p + ktap (so one swizzle per tap suffices: the key
+    depends on the pixel only through p & 15), an outside tap reads the zero
+    pixel, padding lanes stay inside LDS.
+    Bank conflicts: the kernels' comments claim conflict-free fragment reads.
+    Their formulas give that for every read whose lanes are all in the image,
+    and at 13x13 for every read. At 27x27 a read with lanes on the zero pixel
+    (one 128-B pixel, so one bank-window half for all of them) or with clamped
+    padding lanes can be 2-way: 558 + 14 of the 2400 (tap, fragment, K step)
+    reads.
+    Pool tiles: the write p * TB + ((c ^ (p & (NC - 1))) << 4) (c = 4 j + g per
+    wave at 13x13, c = g per group at 27x27) is where the pooling read looks,
+    injective, inside its region; 13x13's four per-wave tiles fit the staged
+    image they overwrite (exactly, at 256 -> 256), 27x27's follows the zero
+    pixel inside the 160 KB a workgroup may use."""
+    s = _DIRECT[name]
+    H = W = s["H"]
+    KS, PAD, CI = s["KS"], s["PAD"], s["CI"]
+    NPIX, CPX, CT = H * W, CI // 8, CI // 32
+    MFT = (NPIX + 15) // 16
+    PXC = (CPX + 15) // 16 * 16 if CPX > 8 else CPX
+    PXB, ZB = PXC * 16, NPIX * PXC * 16
+    LDS = ZB + PXB
+    nfrag = MFT if s["fpw"] is None else s["waves"] * s["fpw"]
+    assert nfrag >= MFT
+
+    def xswz(K):
+        return (K & 7) << 1 if CPX >= 16 else ((K >> 1) & 3) << 1
+
+    # ---- staging
+    place = {}
+    for i in range((NPIX * PXC + 63) // 64):
+        for lane in range(64):
+            ps = i * 64 + lane
+            if ps >= NPIX * PXC:
+                continue
+            K, pc = divmod(ps, PXC)
+            lc = pc ^ xswz(K)
+            assert 0 <= lc < PXC
+            assert ps * 16 == i * 1024 + lane * 16 and ps * 16 + 16 <= ZB
+            if lc < CPX:
+                assert (K, lc) not in place
+                place[(K, lc)] = ps * 16
+    assert len(place) == NPIX * CPX
+    assert LDS <= 160 * 1024
+
+    # ---- operand reads
+    worst = worst_in = 0
+    two_way = {"zero pixel": 0, "clamped lanes": 0}  # 2-way reads by what their lanes touch
+    for tap in range(KS * KS):
+        kh, kw = divmod(tap, KS)
+        ktap = (kh - PAD) * W + kw - PAD
+        for f in range(nfrag):
+            for cc in range(CT):
+                addr, all_in, clamped = [], True, False
+                for lane in range(64):
+                    fr, g = lane & 15, lane >> 4
+                    p = min(16 * f + fr, NPIX - 1)
+                    r, c = divmod(p, W)
+                    inside = 0 <= r + kh - PAD < H and 0 <= c + kw - PAD < W
+                    all_in = all_in and inside and 16 * f + fr < NPIX
+                    clamped = clamped or 16 * f + fr >= NPIX
+                    xa = (p + ktap) * PXB if inside else ZB
+                    tsw = (g << 4) ^ (xswz(fr + ktap) << 4)
+                    a = xa + (tsw ^ (cc * 64))
+                    assert 0 <= a and a + 16 <= LDS, (tap, f, cc, lane)
+                    if 16 * f + fr < NPIX:
+                        if inside:
+                            assert a == place[(p + ktap, 4 * cc + g)], (tap, f, cc, lane)
+                        else:
+                            assert ZB <= a, (tap, f, cc, lane)
+                    addr.append(a)
+                ways = _b128_ways(addr)
+                worst = max(worst, ways)
+                if ways == 2:
+                    two_way["clamped lanes" if clamped else "zero pixel"] += 1
+                if all_in:
+                    worst_in = max(worst_in, ways)
+    assert worst_in == 1 and worst == s["ways"]
+    assert two_way == ({"zero pixel": 558, "clamped lanes": 14} if s["ways"] == 2 else
+                       {"zero pixel": 0, "clamped lanes": 0})
+
+    # ---- pool tiles: the epilogue's write (lane quarter g of group j of the
+    # tile, pixel p) against the pooling loop's read (pooled pixel pp, channel
+    # chunk c, window offset dy, dx), each from its own expression
+    NC = s["NC"]
+    if NC:
+        TB = NC * 16
+
+        def tile_write(p, j, g):
+            return p * TB + (((4 * j + g) ^ (p & (NC - 1))) << 4)
+
+        def tile_read(pp, c, dy, dx):
+            ph, pw = divmod(pp, PO)
+            q = (2 * ph + dy) * W + 2 * pw + dx
+            return q, q * TB + ((c ^ (q & (NC - 1))) << 4)
+
+        PO = (H - 3) // 2 + 1
+        wrote = {}
+        for p in range(NPIX):
+            for j in range(NC // 4):
+                for g in range(4):
+                    off = tile_write(p, j, g)
+                    assert 0 <= off and off + 16 <= NPIX * TB and off not in wrote
+                    wrote[off] = (p, j, g)
+        for pp in range(PO * PO):
+            for c in range(NC):
+                for dy in range(3):
+                    for dx in range(3):
+                        q, off = tile_read(pp, c, dy, dx)
+                        assert q < NPIX and wrote[off] == (q, c // 4, c % 4), (pp, c, dy, dx)
+        if s["tiles"] > 1:  # per-wave tiles over the staged image
+            assert s["tiles"] * NPIX * TB <= ZB
+            if CI == 256:
+                assert s["tiles"] * NPIX * TB == ZB
+        else:  # one tile after the zero pixel
+            assert LDS + NPIX * TB <= 160 * 1024
