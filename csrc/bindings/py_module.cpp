@@ -110,6 +110,38 @@ JpegLayout layout_from_dict(const py::dict& d) {
 }
 
 // a host copy of device descriptors, as jpeg_gpu_plan returned it
+// compute units of the current device
+int device_cus() {
+  hipDeviceProp_t prop;
+  int dev = 0;
+  DMLC_HIP_CHECK(hipGetDevice(&dev));
+  DMLC_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+  return prop.multiProcessorCount;
+}
+
+// a 1x1 / stride-1 conv's ConvArgs for the conv1x1_chain bindings (e4m3 in and out, ReLU)
+ConvArgs chain_conv(uintptr_t x, uintptr_t w, uintptr_t alpha, uintptr_t bias, uintptr_t res, uintptr_t y, int B, int H,
+                    int W, int Cin, int N, float res_scale, float out_inv_scale, bool relu, uintptr_t zero) {
+  ConvArgs a;
+  a.x = P<void>(x);
+  a.w = P<void>(w);
+  a.alpha = P<float>(alpha);
+  a.bias = P<float>(bias);
+  a.res = P<void>(res);
+  a.y = P<void>(y);
+  a.zero = P<void>(zero);
+  a.B = B;
+  a.H = a.Ho = H;
+  a.W = a.Wo = W;
+  a.Cin = a.Kpad = Cin;
+  a.N = a.Npad = a.ldo = N;
+  a.relu = relu;
+  a.in_fp8 = a.out_fp8 = true;
+  a.res_scale = res_scale;
+  a.out_inv_scale = out_inv_scale;
+  return a;
+}
+
 const JpegGpuImage* host_descs(const py::array_t<uint8_t, py::array::c_style>& a, int* n) {
   if (a.size() % (py::ssize_t)sizeof(JpegGpuImage)) throw std::invalid_argument("jpeg descriptors: bad size");
   *n = (int)(a.size() / (py::ssize_t)sizeof(JpegGpuImage));
@@ -142,8 +174,13 @@ PYBIND11_MODULE(_C, m) {
          int Cin, int KH, int KW, int stride, int pad, int N, int Npad, int Kpad, int ldo, bool relu,
          bool out_f32, int split_k, uintptr_t ws, int tile, uintptr_t zero, bool stem, int Ho, int Wo,
          int max_blocks, uintptr_t stream, bool in_fp8, bool out_fp8, uintptr_t alpha, float res_scale,
-         float out_inv_scale, uintptr_t bt_ws, size_t bt_ws_bytes, int bt_splits) {
+         float out_inv_scale, uintptr_t bt_ws, size_t bt_ws_bytes, int bt_splits, int num_cus, uintptr_t x2,
+         int cin2) {
+        if ((x2 || cin2) && tile != kConv1x1Tile)
+          throw std::invalid_argument("conv2d: x2 / cin2 (a second input along K) need the CONV_1X1 route");
         ConvArgs a;
+        a.x2 = P<void>(x2);
+        a.cin2 = cin2;
         a.x = P<void>(x);
         a.zero = P<void>(zero);
         a.stem = stem;
@@ -179,11 +216,7 @@ PYBIND11_MODULE(_C, m) {
         a.out_inv_scale = out_inv_scale;
         if (tile == kConv1x1Tile) {  // weight-stationary 1x1 conv (conv1x1.hip)
           a.tile = -1;
-          hipDeviceProp_t prop;
-          int dev = 0;
-          DMLC_HIP_CHECK(hipGetDevice(&dev));
-          DMLC_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-          conv1x1(a, prop.multiProcessorCount, S(stream));
+          conv1x1(a, num_cus > 0 ? num_cus : device_cus(), S(stream));  // num_cus sizes the persistent grid
           return;
         }
         if (tile == kConv1x1Tile + 2) {  // fully connected (fc_gemm.hip); split_k 0: fc_gemm_splits
@@ -224,7 +257,7 @@ PYBIND11_MODULE(_C, m) {
       py::arg("zero"), py::arg("stem"), py::arg("Ho"), py::arg("Wo"), py::arg("max_blocks"),
       py::arg("stream"), py::arg("in_fp8") = false, py::arg("out_fp8") = false, py::arg("alpha") = 0,
       py::arg("res_scale") = 1.f, py::arg("out_inv_scale") = 1.f, py::arg("bt_ws") = 0, py::arg("bt_ws_bytes") = 0,
-      py::arg("bt_splits") = 1);
+      py::arg("bt_splits") = 1, py::arg("num_cus") = 0, py::arg("x2") = 0, py::arg("cin2") = 0);
   m.def("conv_bigtile_ws_bytes", &conv_bigtile_ws_bytes);
   m.def("conv_bigtile_ws_header_bytes", &conv_bigtile_ws_header_bytes);
   m.def(
@@ -319,6 +352,44 @@ PYBIND11_MODULE(_C, m) {
                  P<float>(b3), P<void>(y), res_scale, out_inv_scale, B, S(stream));
   }, py::arg("x"), py::arg("w1"), py::arg("a1"), py::arg("b1"), py::arg("wf2"), py::arg("b2"), py::arg("wf3"),
      py::arg("b3"), py::arg("y"), py::arg("res_scale"), py::arg("out_inv_scale"), py::arg("B"), py::arg("stream") = 0);
+  m.def("bottleneck56_supported", &bottleneck56_supported, py::arg("H"), py::arg("W"), py::arg("C"), py::arg("Cm"));
+  m.def("bottleneck56_head", [](uintptr_t x, uintptr_t w1, uintptr_t b1, uintptr_t wf2, uintptr_t b2, uintptr_t y, int B,
+                                uintptr_t stream) {
+    bottleneck56_head(P<void>(x), P<void>(w1), P<float>(b1), P<void>(wf2), P<float>(b2), P<void>(y), B, S(stream));
+  }, py::arg("x"), py::arg("w1"), py::arg("b1"), py::arg("wf2"), py::arg("b2"), py::arg("y"), py::arg("B"),
+     py::arg("stream") = 0);
+  // conv1x1_chain: the expand conv (x [B,H,W,Cin] e4m3 -> y [B,H,W,N] e4m3, + res) and the reduce conv on y
+  // (-> y2 [B,H,W,N2] e4m3); the *_supported form takes the same arguments and launches nothing
+  auto chain_args = [](uintptr_t x, uintptr_t w, uintptr_t alpha, uintptr_t bias, uintptr_t res, uintptr_t y,
+                       uintptr_t w2, uintptr_t alpha2, uintptr_t bias2, uintptr_t y2, int B, int H, int W, int Cin,
+                       int N, int N2, float res_scale, float out_inv_scale, float out_inv_scale2, bool relu, bool relu2,
+                       uintptr_t zero) {
+    return std::make_pair(
+        chain_conv(x, w, alpha, bias, res, y, B, H, W, Cin, N, res_scale, out_inv_scale, relu, zero),
+        chain_conv(y, w2, alpha2, bias2, 0, y2, B, H, W, N, N2, 1.f, out_inv_scale2, relu2, zero));
+  };
+  m.def("conv1x1_chain_supported", [=](uintptr_t x, uintptr_t w, uintptr_t alpha, uintptr_t bias, uintptr_t res,
+                                       uintptr_t y, uintptr_t w2, uintptr_t alpha2, uintptr_t bias2, uintptr_t y2, int B,
+                                       int H, int W, int Cin, int N, int N2, float res_scale, float out_inv_scale,
+                                       float out_inv_scale2, bool relu, bool relu2, uintptr_t zero) {
+    const auto ar = chain_args(x, w, alpha, bias, res, y, w2, alpha2, bias2, y2, B, H, W, Cin, N, N2, res_scale,
+                               out_inv_scale, out_inv_scale2, relu, relu2, zero);
+    return conv1x1_chain_supported(ar.first, ar.second);
+  }, py::arg("x"), py::arg("w"), py::arg("alpha"), py::arg("bias"), py::arg("res"), py::arg("y"), py::arg("w2"),
+     py::arg("alpha2"), py::arg("bias2"), py::arg("y2"), py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"),
+     py::arg("N"), py::arg("N2"), py::arg("res_scale") = 1.f, py::arg("out_inv_scale") = 1.f,
+     py::arg("out_inv_scale2") = 1.f, py::arg("relu") = true, py::arg("relu2") = true, py::arg("zero") = 0);
+  m.def("conv1x1_chain", [=](uintptr_t x, uintptr_t w, uintptr_t alpha, uintptr_t bias, uintptr_t res, uintptr_t y,
+                             uintptr_t w2, uintptr_t alpha2, uintptr_t bias2, uintptr_t y2, int B, int H, int W, int Cin,
+                             int N, int N2, float res_scale, float out_inv_scale, float out_inv_scale2, bool relu,
+                             bool relu2, uintptr_t zero, int num_cus, uintptr_t stream) {
+    const auto ar = chain_args(x, w, alpha, bias, res, y, w2, alpha2, bias2, y2, B, H, W, Cin, N, N2, res_scale,
+                               out_inv_scale, out_inv_scale2, relu, relu2, zero);
+    conv1x1_chain(ar.first, ar.second, num_cus > 0 ? num_cus : device_cus(), S(stream));
+  }, py::arg("x"), py::arg("w"), py::arg("alpha"), py::arg("bias"), py::arg("res"), py::arg("y"), py::arg("w2"),
+     py::arg("alpha2"), py::arg("bias2"), py::arg("y2"), py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"),
+     py::arg("N"), py::arg("N2"), py::arg("res_scale"), py::arg("out_inv_scale"), py::arg("out_inv_scale2"),
+     py::arg("relu"), py::arg("relu2"), py::arg("zero"), py::arg("num_cus") = 0, py::arg("stream") = 0);
   // AlexNet's shape-specialised kernels
   m.attr("ALEX_STEM_K") = kAlexStemK;
   m.def("alex_stem_k", &alex_stem_k);

@@ -250,7 +250,16 @@ void conv5x5_27(const void* x, const void* wf, const float* bias, void* y, const
 // ResNet50 layer1 identity bottleneck (resnet50_fp8 layer1.1 / 1.2) in one
 // kernel (bottleneck56.hip): x, y e4m3 [B,56,56,256]; w1 e4m3 [64][256] with
 // a1 = s_x * s_w1; wf2 / wf3: fragment-order bf16 weights (stream_frag_index,
-// K = 576 / 64); y = relu(conv3(relu(conv2(relu(conv1(x))))) + x) / s_y.
+// K = 576 / 64); y = relu(conv3(relu(conv2(relu(conv1(x))))) + x) / s_y,
+// with 1 / s_y = out_inv_scale folded in before conv3, not applied after it:
+// the kernel multiplies wf3 by out_inv_scale in fp32 and RE-ROUNDS the
+// product to bf16 (conv3's MFMA operand), and b3 * out_inv_scale (fp32) is
+// the MFMA's accumulator input; the residual is e4m3(x) * (res_scale *
+// out_inv_scale), one fp32 fma onto the accumulator, then the clamp to
+// [0, 448] and the e4m3 rounding. A reference has to model the re-rounded
+// weights bf16(fp32(w3) * fp32(out_inv_scale)): with an out_inv_scale that is
+// no power of two they differ from w3 / s_y by up to 2^-9 relative each.
+// t1 and t2 are rounded to bf16 (LDS); conv1 is relu(fma(acc, a1, b1)).
 bool bottleneck56_supported(int H, int W, int C, int Cm);
 void bottleneck56(const void* x, const void* w1, const float* a1, const float* b1, const void* wf2, const float* b2,
                   const void* wf3, const float* b3, void* y, float res_scale, float out_inv_scale, int B,

@@ -103,12 +103,17 @@ def conv2d(x: torch.Tensor, w_packed: torch.Tensor, cout: int, kh: int, kw: int,
            pad: int = 0, bias: torch.Tensor | None = None, res: torch.Tensor | None = None,
            relu: bool = False, out_f32: bool = False, split_k: int = 1, tile: int = -1,
            out: torch.Tensor | None = None, stem: bool = False, out_hw: tuple | None = None,
-           max_blocks: int = 0, ws: torch.Tensor | None = None) -> torch.Tensor:
+           max_blocks: int = 0, ws: torch.Tensor | None = None, num_cus: int = 0,
+           x2: torch.Tensor | None = None) -> torch.Tensor:
     """Implicit-GEMM conv on MFMA. x: bf16 NHWC [B,H,W,Cin] (Cin % 64 == 0),
     or with ``stem`` the padded packed RGB image (``stem_image``) plus the
     output size ``out_hw`` (the padding is already in the image).
-    Returns [B,Ho,Wo,cout] (bf16, or fp32 if out_f32)."""
-    _need_cuda(x, w_packed, bias, res)
+    Returns [B,Ho,Wo,cout] (bf16, or fp32 if out_f32).
+
+    tile=CONV_1X1 only: ``num_cus`` sizes the persistent grid (0: the
+    device's count), and ``x2`` [B,H,W,cin2] is a second bf16 input
+    concatenated along K (w_packed = [W | W2], K = Cin + cin2)."""
+    _need_cuda(x, w_packed, bias, res, x2)
     C = native()
     B, H, W, Cin = x.shape
     if stem:
@@ -137,8 +142,15 @@ def conv2d(x: torch.Tensor, w_packed: torch.Tensor, cout: int, kh: int, kw: int,
              W=W, Cin=Cin, KH=kh, KW=kw, stride=stride, pad=pad, N=cout, Npad=w_packed.shape[0],
              Kpad=w_packed.shape[1], ldo=cout, relu=relu, out_f32=out_f32, split_k=split_k, ws=_ptr(ws),
              tile=tile, zero=_ptr(_zero_page(x.device)), stem=stem, Ho=Ho, Wo=Wo, max_blocks=max_blocks,
-             stream=_stream(), bt_ws=_ptr(bt_ws), bt_ws_bytes=bt_bytes, bt_splits=bt_splits)
+             stream=_stream(), bt_ws=_ptr(bt_ws), bt_ws_bytes=bt_bytes, bt_splits=bt_splits, num_cus=num_cus,
+             x2=_ptr(None if x2 is None else _second_input(x, x2)), cin2=0 if x2 is None else x2.shape[-1])
     return out
+
+
+def _second_input(x: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
+    if x2.dim() != 4 or tuple(x2.shape[:3]) != tuple(x.shape[:3]) or x2.dtype != x.dtype or not x2.is_contiguous():
+        raise ValueError("conv2d: x2 must be a contiguous [B,H,W,cin2] tensor of x's dtype")
+    return x2
 
 
 _BT_WS: dict = {}
@@ -446,18 +458,20 @@ def pack_conv_weight_fp8(w: torch.Tensor, device=None) -> tuple[torch.Tensor, to
 def conv2d_fp8(x: torch.Tensor, w_q: torch.Tensor, alpha: torch.Tensor, cout: int, kh: int, kw: int,
                stride: int = 1, pad: int = 0, bias: torch.Tensor | None = None, res: torch.Tensor | None = None,
                res_scale: float = 1.0, relu: bool = False, out_scale: float | None = None,
-               tile: int = -1) -> torch.Tensor:
+               tile: int = -1, out: torch.Tensor | None = None, num_cus: int = 0,
+               x2: torch.Tensor | None = None) -> torch.Tensor:
     """fp8 implicit-GEMM conv (block-scaled e4m3 MFMA). x: e4m3 NHWC
     (Cin % 128 == 0) or bf16 (then w_q is bf16-packed and alpha unused).
     alpha = s_x * s_w[n]; residual e4m3 scaled by res_scale; output e4m3
-    with scale out_scale (or bf16 when out_scale is None)."""
-    _need_cuda(x, w_q, alpha, bias, res)
+    with scale out_scale (or bf16 when out_scale is None). ``out``: the
+    output tensor to write; ``num_cus`` / ``x2``: as for ``conv2d``."""
+    _need_cuda(x, w_q, alpha, bias, res, out, x2)
     C = native()
     B, H, W, Cin = x.shape
     in8 = x.dtype == FP8
     Ho, Wo = C.conv_out_dim(H, kh, stride, pad), C.conv_out_dim(W, kw, stride, pad)
     out8 = out_scale is not None
-    y = torch.empty(B, Ho, Wo, cout, device=x.device, dtype=FP8 if out8 else torch.bfloat16)
+    y = _out_tensor(out, (B, Ho, Wo, cout), FP8 if out8 else torch.bfloat16, x.device, "conv2d_fp8")
     if bias is not None:
         bias = bias.float().contiguous()
         if bias.numel() < w_q.shape[0]:
@@ -467,8 +481,122 @@ def conv2d_fp8(x: torch.Tensor, w_q: torch.Tensor, alpha: torch.Tensor, cout: in
              KH=kh, KW=kw, stride=stride, pad=pad, N=cout, Npad=w_q.shape[0], Kpad=w_q.shape[1], ldo=cout,
              relu=relu, out_f32=False, split_k=1, ws=0, tile=tile, zero=_ptr(_zero_page(x.device)), stem=False,
              Ho=Ho, Wo=Wo, max_blocks=0, stream=_stream(), in_fp8=in8, out_fp8=out8, alpha=_ptr(al),
-             res_scale=res_scale, out_inv_scale=(1.0 / out_scale) if out8 else 1.0)
+             res_scale=res_scale, out_inv_scale=(1.0 / out_scale) if out8 else 1.0, num_cus=num_cus,
+             x2=_ptr(None if x2 is None else _second_input(x, x2)), cin2=0 if x2 is None else x2.shape[-1])
     return y
+
+
+def _out_tensor(out, shape, dtype, device, what: str) -> torch.Tensor:
+    """``out`` checked (contiguous, shape, dtype; e4m3 also as uint8 bytes), or a new tensor."""
+    if out is None:
+        return torch.empty(*shape, device=device, dtype=dtype)
+    _need_cuda(out)
+    ok = out.dtype == dtype or (dtype == FP8 and out.dtype == torch.uint8)
+    if tuple(out.shape) != tuple(shape) or not ok or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous {tuple(shape)} tensor of {dtype}")
+    return out
+
+
+def _e4m3(t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dtype not in (FP8, torch.uint8):
+        raise ValueError(f"{what} must be e4m3 (float8_e4m3fn, or its bytes as uint8)")
+    return t.contiguous()
+
+
+def _f32(t: torch.Tensor, n: int, what: str) -> torch.Tensor:
+    if t.numel() < n:
+        raise ValueError(f"{what} holds {n} values")
+    return t.float().contiguous()
+
+
+def bottleneck56(x: torch.Tensor, w1_q: torch.Tensor, a1: torch.Tensor, b1: torch.Tensor, w2_packed: torch.Tensor,
+                 b2: torch.Tensor, w3_packed: torch.Tensor, b3: torch.Tensor, res_scale: float, out_scale: float,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """ResNet50's layer1 identity bottleneck as one kernel (bottleneck56.hip)
+    on e4m3 NHWC [B,56,56,256] (value = code * res_scale):
+      t1 = bf16(relu(conv1x1(x codes, w1_q codes) * a1 + b1))   64 channels
+      t2 = bf16(relu(conv3x3(t1, w2) + b2))                     64 channels
+      y  = e4m3(relu(conv1x1(t2, w3) + b3 + x) / out_scale)     256 channels
+    w1_q / a1: ``pack_conv_weight_fp8`` of the [64,256,1,1] weights, a1 =
+    s_x * s_w1; w2_packed [64, 576] and w3_packed [256, 64]: ``pack_conv_weight``
+    (bf16). conv3's weights are re-rounded to bf16 after the multiplication
+    by 1 / out_scale (kernels.h). ``out``: the e4m3 output to write."""
+    _need_cuda(x, w1_q, a1, b1, w2_packed, b2, w3_packed, b3, out)
+    C = native()
+    if x.dim() != 4:
+        raise ValueError("bottleneck56: x is e4m3 NHWC [B,56,56,256]")
+    B, H, W, Cin = x.shape
+    if not C.bottleneck56_supported(H, W, Cin, 64) or tuple(w1_q.shape[-2:]) != (64, 256) \
+            or tuple(w2_packed.shape) != (64, 576) or tuple(w3_packed.shape) != (256, 64) \
+            or w2_packed.dtype != torch.bfloat16 or w3_packed.dtype != torch.bfloat16:
+        raise ValueError("bottleneck56: unsupported shape / dtype")
+    x, w1_q = _e4m3(x, "bottleneck56: x"), _e4m3(w1_q, "bottleneck56: w1_q")
+    y = _out_tensor(out, (B, H, W, Cin), FP8, x.device, "bottleneck56")
+    if y.data_ptr() == x.data_ptr():
+        raise ValueError("bottleneck56: in-place not supported")
+    wf2, wf3 = stream_weight_frag(w2_packed), stream_weight_frag(w3_packed)
+    C.bottleneck56(_ptr(x), _ptr(w1_q), _ptr(_f32(a1, 64, "a1")), _ptr(_f32(b1, 64, "b1")), _ptr(wf2),
+                   _ptr(_f32(b2, 64, "b2")), _ptr(wf3), _ptr(_f32(b3, 256, "b3")), _ptr(y), float(res_scale),
+                   1.0 / float(out_scale), B, _stream())
+    return y
+
+
+def bottleneck56_head(x: torch.Tensor, w1_packed: torch.Tensor, b1: torch.Tensor, w2_packed: torch.Tensor,
+                      b2: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """ResNet50 layer1.0's reduce 1x1 + 3x3 convs as one kernel
+    (bottleneck56.hip) on bf16 NHWC [B,56,56,64]:
+    relu(conv3x3(bf16(relu(conv1x1(x) + b1))) + b2), bf16 [B,56,56,64].
+    w1_packed [64, 64], w2_packed [64, 576]: ``pack_conv_weight``."""
+    _need_cuda(x, w1_packed, b1, w2_packed, b2, out)
+    C = native()
+    if x.dim() != 4:
+        raise ValueError("bottleneck56_head: x is bf16 NHWC [B,56,56,64]")
+    B, H, W, Cin = x.shape
+    if not C.bottleneck56_supported(H, W, 4 * Cin, Cin) or x.dtype != torch.bfloat16 \
+            or tuple(w1_packed.shape) != (64, 64) or tuple(w2_packed.shape) != (64, 576) \
+            or w1_packed.dtype != torch.bfloat16 or w2_packed.dtype != torch.bfloat16:
+        raise ValueError("bottleneck56_head: unsupported shape / dtype")
+    x = x.contiguous()
+    y = _out_tensor(out, (B, H, W, Cin), torch.bfloat16, x.device, "bottleneck56_head")
+    if y.data_ptr() == x.data_ptr():
+        raise ValueError("bottleneck56_head: in-place not supported")
+    C.bottleneck56_head(_ptr(x), _ptr(w1_packed.contiguous()), _ptr(_f32(b1, 64, "b1")),
+                        _ptr(stream_weight_frag(w2_packed)), _ptr(_f32(b2, 64, "b2")), _ptr(y), B, _stream())
+    return y
+
+
+def conv1x1_chain(x: torch.Tensor, w_q: torch.Tensor, alpha: torch.Tensor, bias: torch.Tensor, res: torch.Tensor,
+                  res_scale: float, out_scale: float, w2_q: torch.Tensor, alpha2: torch.Tensor, bias2: torch.Tensor,
+                  out_scale2: float, num_cus: int = 0, out: torch.Tensor | None = None,
+                  out2: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """A bottleneck's e4m3 expand conv and the next bottleneck's reduce conv on
+    its output in one launch (conv1x1.hip's chained form), both 1x1 / stride 1
+    with ReLU: y = e4m3(relu(x . w * alpha + bias + res * res_scale) /
+    out_scale) [B,H,W,512] from x [B,H,W,128], y2 = e4m3(relu(y codes . w2 *
+    alpha2 + bias2) / out_scale2) [B,H,W,128] (alpha2 = out_scale * s_w2).
+    w_q / w2_q: ``pack_conv_weight_fp8``. num_cus sizes the persistent grid
+    (0: the device's count). Returns (y, y2); ``out`` / ``out2`` to write."""
+    _need_cuda(x, w_q, alpha, bias, res, w2_q, alpha2, bias2, out, out2)
+    C = native()
+    if x.dim() != 4 or w_q.dim() != 2 or w2_q.dim() != 2:
+        raise ValueError("conv1x1_chain: x is e4m3 NHWC, the weights are packed [N, K]")
+    B, H, W, Cin = x.shape
+    N, N2 = w_q.shape[0], w2_q.shape[0]
+    if w_q.shape[1] != Cin or w2_q.shape[1] != N or tuple(res.shape) != (B, H, W, N):
+        raise ValueError("conv1x1_chain: operand shapes")
+    x, res = _e4m3(x, "conv1x1_chain: x"), _e4m3(res, "conv1x1_chain: res")
+    w_q, w2_q = _e4m3(w_q, "conv1x1_chain: w_q"), _e4m3(w2_q, "conv1x1_chain: w2_q")
+    y = _out_tensor(out, (B, H, W, N), FP8, x.device, "conv1x1_chain")
+    y2 = _out_tensor(out2, (B, H, W, N2), FP8, x.device, "conv1x1_chain")
+    args = dict(x=_ptr(x), w=_ptr(w_q), alpha=_ptr(_f32(alpha, N, "alpha")), bias=_ptr(_f32(bias, N, "bias")),
+                res=_ptr(res), y=_ptr(y), w2=_ptr(w2_q), alpha2=_ptr(_f32(alpha2, N2, "alpha2")),
+                bias2=_ptr(_f32(bias2, N2, "bias2")), y2=_ptr(y2), B=B, H=H, W=W, Cin=Cin, N=N, N2=N2,
+                res_scale=float(res_scale), out_inv_scale=1.0 / float(out_scale),
+                out_inv_scale2=1.0 / float(out_scale2), relu=True, relu2=True, zero=_ptr(_zero_page(x.device)))
+    if not C.conv1x1_chain_supported(**args):
+        raise ValueError("conv1x1_chain: unsupported pair of convs")
+    C.conv1x1_chain(**args, num_cus=num_cus, stream=_stream())
+    return y, y2
 
 
 def stream8_weight_frag(w_q: torch.Tensor, cout: int) -> torch.Tensor:

@@ -35,6 +35,14 @@ def quantise(rows, metric="dot"):
     return codes, scale, e
 
 
+def round_bytes(v):
+    """e4m3fn(v) as uint8 bytes, by the same conversion as `quantise` (nearest even, subnormals kept); v finite,
+    |v| <= 448 and exact in float32."""
+    v32 = v.to(torch.float32)
+    assert torch.equal(v32.to(torch.float64), v.to(torch.float64)) and float(v32.abs().max()) <= 448
+    return v32.to(torch.float8_e4m3fn).view(torch.uint8)
+
+
 def dequantise(codes, e):
     """codes 2^-e as float32: exact, and a bf16 value (4 significant bits)."""
     return torch.ldexp(codes.to(torch.float64), -e[:, None]).to(torch.float32)

@@ -1,5 +1,6 @@
 """The element-wise bar of the op tests (test_kernels_fused_gpu.py,
-test_kernels_resnet_gpu.py, test_kernel_bar_cpu.py): a kernel's output against
+test_kernels_resnet_gpu.py, test_kernels_resnet50_gpu.py,
+test_kernel_bar_cpu.py): a kernel's output against
 the float64 result on the same bf16-rounded operands.
 
 A rounding argument, not a measurement. A bf16-output conv or fc with K
@@ -46,7 +47,9 @@ Roundings beyond that derivation, each stated where it is used:
    ends agree (most elements) t is known exactly, elsewhere it is one of two
    neighbouring bf16 values. With delta the width of that interval the
    reference relu(conv2(bf16r(v)) + b2 + x) is off by at most conv2(delta,
-   |w2|) on that account, which is added to conv2's own bar;
+   |w2|) on that account, which is added to conv2's own bar. `chain` is the
+   same argument for n stages (bottleneck56: an e4m3 conv1 with a per-channel
+   alpha, a 3x3, and an e4m3 conv3 with a residual; bottleneck56_head);
  * an e4m3 output relu(v) inv_scale (`e4m3_bound`): e4m3 keeps 4 significant
    bits, unit roundoff 2^-4 of the value by the argument above; below its
    smallest normal 2^-6 the values step by 2^-9, half a step is 2^-10. In the
@@ -58,7 +61,8 @@ a zero padding selects (every window holds a value >= 0).
 
 Measured on an MI355X: the worst |err| / bar of any kernel is 0.99 (the 1x1
 downsample outputs, K = 64; alex_stem 0.95), per kernel in the docstrings of
-test_kernels_fused_gpu.py and test_kernels_resnet_gpu.py.
+test_kernels_fused_gpu.py, test_kernels_resnet_gpu.py and
+test_kernels_resnet50_gpu.py.
 
 Next to the bar every test keeps the project's relative-L2 bar for bf16
 outputs (5e-3), and a negative control: a reference with one realistic kernel
@@ -138,19 +142,65 @@ def e4m3_bound(ref, mag, K, inv_scale):
     return K * EPS_SUM * mag * inv_scale + (E4M3_EPS * v).clamp_min(E4M3_HALF_STEP)
 
 
+def chain(x, stages, alpha=None, res=None, e4m3_inv=None):
+    """n chained stride-1 convs with bf16 intermediates (conv3x3_block,
+    bottleneck56, bottleneck56_head). stages: [(w, bias, K, pad), ...], the
+    last one's output bf16, or e4m3 with `e4m3_inv` (its inv_scale); every
+    other stage i leaves t_i = bf16r(relu(v_i)). Returns (ref64 before the
+    last ReLU, its bar, [delta_i], [t_i]), NCHW float64.
+
+    The interval argument of the module text, stage by stage: the kernel's
+    fp32 value of t_i lies within s_i of the float64 v_i, s_i the conv's own
+    summation slack K_i 2^-23 mag_i plus what the uncertainty of its input
+    can move it, conv_i(delta_{i-1}, |w_i|); so the stored t_i lies in
+    [bf16r(relu(v_i - s_i)), bf16r(relu(v_i + s_i))], of width delta_i, which
+    goes through the next conv's |w| into that conv's slack and, at the last
+    stage, onto its bar (times inv_scale for an e4m3 output).
+
+    alpha (per output channel, with an e4m3 first input: conv1 of
+    bottleneck56): the first stage is relu(acc alpha + bias), one fp32 fma on
+    the fp32 sum of exact products, inside K 2^-23 mag with mag = conv(|x|,
+    |w|) |alpha| + |bias|. res (NCHW float64, already scaled): the last
+    stage's residual, in its mag."""
+    t, delta, deltas, ts = x, None, [], []
+    for i, (w, bias, K, pad) in enumerate(stages):
+        last = i == len(stages) - 1
+        r = res if last else None
+        if i == 0 and alpha is not None:
+            a, b = alpha.double().view(1, -1, 1, 1), bias.double().view(1, -1, 1, 1)
+            v = F.conv2d(t.double(), w.double(), None, 1, pad) * a + b
+            mag = F.conv2d(t.double().abs(), w.double().abs(), None, 1, pad) * a.abs() + b.abs()
+            if r is not None:
+                v, mag = v + r.double(), mag + r.double().abs()
+        else:
+            v, mag = conv_ref(t, w, bias, 1, pad, res=r)
+        if last:
+            if e4m3_inv is None:
+                bnd = bound(torch.relu(v), mag, K)
+                if delta is not None:
+                    bnd = bnd + F.conv2d(delta, w.double().abs(), None, 1, pad)
+            else:
+                bnd = e4m3_bound(torch.relu(v), mag, K, e4m3_inv)
+                if delta is not None:
+                    bnd = bnd + F.conv2d(delta, w.double().abs(), None, 1, pad) * e4m3_inv
+            return v, bnd, deltas, ts
+        s = K * EPS_SUM * mag
+        if delta is not None:
+            s = s + F.conv2d(delta, w.double().abs(), None, 1, pad)
+        lo, hi = bf16r(torch.relu(v - s)), bf16r(torch.relu(v + s))
+        t = bf16r(torch.relu(v))
+        assert bool((lo <= t).all()) and bool((t <= hi).all())
+        delta = hi - lo
+        deltas.append(delta)
+        ts.append(t)
+
+
 def chained(x, w1, b1, w2, b2, K=576, pad=1):
     """Two chained 3x3 convs with a bf16 intermediate and the input as the
     residual (conv3x3_block): (ref64 before the last ReLU, its bar, delta,
     the intermediate bf16r(v)), NCHW float64. See the module text."""
-    v, mag1 = conv_ref(x, w1, b1, 1, pad)
-    s1 = K * EPS_SUM * mag1
-    lo, hi = bf16r(torch.relu(v - s1)), bf16r(torch.relu(v + s1))
-    t = bf16r(torch.relu(v))
-    assert bool((lo <= t).all()) and bool((t <= hi).all())
-    delta = hi - lo
-    ref, mag2 = conv_ref(t, w2, b2, 1, pad, res=x)
-    bnd = bound(torch.relu(ref), mag2, K) + F.conv2d(delta, w2.double().abs(), None, 1, pad)
-    return ref, bnd, delta, t
+    ref, bnd, deltas, ts = chain(x, [(w1, b1, K, pad), (w2, b2, K, pad)], res=x)
+    return ref, bnd, deltas[0], ts[0]
 
 
 def block_operands(B, seed):
@@ -222,13 +272,13 @@ def fault_border_taps_s2(ref, x, w, at=0):
     return out
 
 
-def fault_chunk_swap(ref, b=0, h=None, w=None, chunk=1):
-    """One 8-channel chunk of one pixel swapped with its right neighbour's (a
-    swizzle slip)."""
+def fault_chunk_swap(ref, b=0, h=None, w=None, chunk=1, width=8):
+    """One 8-channel chunk (16 B of bf16; width = 16: 16 B of e4m3) of one
+    pixel swapped with its right neighbour's (a swizzle slip)."""
     h = ref.shape[2] // 2 if h is None else h
     w = ref.shape[3] // 2 if w is None else w
     out = ref.clone()
-    c = slice(8 * chunk, 8 * chunk + 8)
+    c = slice(width * chunk, width * chunk + width)
     out[b, c, h, w], out[b, c, h, w + 1] = ref[b, c, h, w + 1], ref[b, c, h, w]
     return out
 
@@ -303,6 +353,188 @@ def block_controls(x, w1, b1, w2, b2, ring):
     return out + [("conv2 " + n, r) for n, r in faults(ref, t, w2)]
 
 
+# ---------------------------------------------------------------- bottleneck56 / bottleneck56_head (ResNet50 layer1)
+def f32(v):
+    """A Python float rounded to fp32 (a kernel argument), as a float."""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def e4m3_weights(w):
+    """ops.pack_conv_weight_fp8's quantisation of [Cout, Cin, 1, 1] weights:
+    (codes as float64 [Cout, Cin, 1, 1], fp32 per-row scales [Cout])."""
+    w2 = w.float().reshape(w.shape[0], -1)
+    s = (w2.abs().amax(1) / E4M3_MAX).clamp_min(1e-12)
+    q = (w2 / s[:, None]).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    return q.double().reshape(w.shape), s
+
+
+def bottleneck_operands(B, seed):
+    """bottleneck56's random operands (the GPU bar test and the CPU check of
+    its controls share them), NCHW float64: x, w1 e4m3 codes (x >= 0 like the
+    post-ReLU activation it is), a1 = s_x s_w1 (fp32), bf16 w2 / w3, fp32
+    biases (b1 with a positive offset: its ReLU is what wrong padding holds),
+    and an output scale that is no power of two, chosen so that the largest
+    output sits at 400 of e4m3's 448."""
+    g = torch.Generator().manual_seed(seed)
+    xv = torch.rand(B, 256, 56, 56, generator=g) * 4
+    sx = f32(float(xv.max()) / E4M3_MAX)
+    o = {"x": (xv / sx).clamp(0, E4M3_MAX).to(torch.float8_e4m3fn).double(), "res_scale": sx}
+    o["w1"], s1 = e4m3_weights(torch.randn(64, 256, 1, 1, generator=g) / 32)
+    o["a1"] = (sx * s1).float().double()
+    o["b1"] = (torch.randn(64, generator=g) * 0.1 + 0.25).float().double()
+    o["w2"] = (torch.randn(64, 64, 3, 3, generator=g) / 24).bfloat16().double()
+    o["b2"] = (torch.randn(64, generator=g) * 0.1).float().double()
+    o["w3"] = (torch.randn(256, 64, 1, 1, generator=g) / 8).bfloat16().double()
+    o["b3"] = (torch.randn(256, generator=g) * 0.1).float().double()
+    o["out_scale"] = 1.0
+    top = float(torch.relu(bottleneck_ref(o)[0]).max())
+    o["out_scale"] = top / 400.0
+    return o
+
+
+def bottleneck_last(o):
+    """bottleneck56's last stage in the output's units, as the kernel forms
+    it (kernels.h): (bf16r(fp32(w3) fp32(inv)), fp32(b3 inv), the residual
+    x fp32(res_scale inv)), inv = fp32(1 / out_scale)."""
+    inv = torch.tensor(1.0 / o["out_scale"], dtype=torch.float32)
+    w3s = bf16r(o["w3"].float() * inv)
+    b3s = (o["b3"].float() * inv).double()
+    rsi = (torch.tensor(o["res_scale"], dtype=torch.float32) * inv).double()
+    return w3s, b3s, o["x"] * rsi
+
+
+def bottleneck_ref(o, bar=True):
+    """(ref64 in the output's units before the last ReLU, its bar, deltas,
+    [t1, t2]) of bottleneck56. bar = False (operands that saturate e4m3: the
+    exact-integer ones): the second item is not the output's bar."""
+    w3s, b3s, res = bottleneck_last(o)
+    return chain(o["x"], [(o["w1"], o["b1"], 256, 0), (o["w2"], o["b2"], 576, 1), (w3s, b3s, 64, 0)],
+                 alpha=o["a1"], res=res, e4m3_inv=1.0 if bar else None)
+
+
+def head_operands(B, seed):
+    """bottleneck56_head's random operands, NCHW float64 (bf16 values)."""
+    g = torch.Generator().manual_seed(seed)
+    o = {"x": torch.relu(torch.randn(B, 64, 56, 56, generator=g)).bfloat16().double()}
+    o["w1"] = (torch.randn(64, 64, 1, 1, generator=g) / 8).bfloat16().double()
+    o["b1"] = (torch.randn(64, generator=g) * 0.1 + 0.25).float().double()
+    o["w2"] = (torch.randn(64, 64, 3, 3, generator=g) / 24).bfloat16().double()
+    o["b2"] = (torch.randn(64, generator=g) * 0.1).float().double()
+    return o
+
+
+def head_ref(o):
+    return chain(o["x"], [(o["w1"], o["b1"], 64, 0), (o["w2"], o["b2"], 576, 1)])
+
+
+def fault_t1_padding(v2, t1, w2, b1, rows):
+    """conv2 (3x3 / p1 on t1) whose padding rows (rows = True: t1 rows -1 and
+    H) or columns (-1 and W) hold bf16r(relu(b1)), a conv1 of zeros, where
+    they should hold 0."""
+    fill = bf16r(torch.relu(b1.double())).view(1, -1, 1, 1)
+    tp = F.pad(t1, (1, 1, 1, 1))
+    extra = torch.zeros_like(tp)
+    if rows:
+        extra[:, :, 0, 1:-1] = fill[..., 0]
+        extra[:, :, -1, 1:-1] = fill[..., 0]
+    else:
+        extra[:, :, 1:-1, 0] = fill[..., 0]
+        extra[:, :, 1:-1, -1] = fill[..., 0]
+    return v2 + F.conv2d(extra, w2.double(), None, 1, 0)
+
+
+def conv2_faults(v2, t1, w2, b1, ring, seam=28):
+    """The faults of the bottleneck kernels' 3x3 conv on the t1 ring, as
+    faulty float64 conv2 outputs (before its ReLU): border taps next to the
+    top padding and at a step seam (t1 row `seam` = 4k, the last row the
+    previous step's conv1 wrote), padding that is not zero, a ring row stale
+    by `ring`."""
+    return [("border taps row 0", fault_border_taps(v2, t1, w2, 1)),
+            ("border taps seam", fault_border_taps(v2, t1, w2, 1, at=seam)),
+            ("t1 padding rows", fault_t1_padding(v2, t1, w2, b1, True)),
+            ("t1 padding columns", fault_t1_padding(v2, t1, w2, b1, False)),
+            ("ring row", fault_ring_row(v2, t1, w2, 4 * (ring // 4) + 1, ring))]
+
+
+def bottleneck_controls(o, ring):
+    """bottleneck56's faulty references in the output's units (before the
+    last ReLU): conv2's faults carried through conv3, and the faults of the
+    output itself."""
+    w3s, b3s, res = bottleneck_last(o)
+    ref, _, _, (t1, t2) = bottleneck_ref(o, bar=False)
+    v2, _ = conv_ref(t1, o["w2"], o["b2"], 1, 1)
+    out = [(n, conv_ref(bf16r(torch.relu(w)), w3s, b3s, 1, 0, res=res)[0])
+           for n, w in conv2_faults(v2, t1, o["w2"], o["b1"], ring)]
+    B = ref.shape[0]
+    out.append(("y chunk swap", fault_chunk_swap(ref, b=B - 1, h=55, w=54, chunk=5, width=16)))
+    inv = f32(1.0 / o["out_scale"])
+    out.append(("residual without res_scale", ref - res + o["x"] * inv))
+    if B > 1:
+        out.append(("batch shift", fault_batch_shift(ref)))
+    return out
+
+
+def head_controls(o, ring):
+    ref, _, _, (t1,) = head_ref(o)
+    out = conv2_faults(ref, t1, o["w2"], o["b1"], ring)
+    if ref.shape[0] > 1:
+        out.append(("batch shift", fault_batch_shift(ref)))
+    return out
+
+
+def _sparse(cout, cin, k, entries, g):
+    """[cout, cin, k, k] float64 with `entries` non-zero integer weights per
+    output channel, walking the input channels and the taps in turn so that
+    every one of them is used."""
+    w = torch.zeros(cout, cin, k, k, dtype=torch.float64)
+    vals = torch.tensor([1.0, -1.0, 2.0, 1.0, -2.0])
+    for n in range(cout):
+        for j in range(entries):
+            e = n * entries + j
+            tap = (e + n // 9) % (k * k)
+            w[n, (e * 5) % cin, tap // k, tap % k] = vals[int(torch.randint(0, 5, (1,), generator=g))]
+    return w
+
+
+def bottleneck_exact_operands(B, seed=0):
+    """Small dyadic integers for which every fp32 value inside bottleneck56
+    is exact, so its output bytes are known exactly: x codes 1..3, sparse
+    integer weights, a1 in {1, 2, 4}, integer biases (b1 up to 6: non-zero t1
+    padding shows), res_scale = 4 and 1 / out_scale = 1 / 2 (powers of two);
+    t1 <= 54 and t2 <= 256 are integers, exact in bf16. The final values
+    include negatives, ties of the e4m3 grid and a few above 448."""
+    g = torch.Generator().manual_seed(seed)
+    o = {"x": torch.randint(1, 4, (B, 256, 56, 56), generator=g).double(), "res_scale": 4.0, "out_scale": 2.0}
+    o["w1"] = _sparse(64, 256, 1, 4, g).sign()
+    o["a1"] = torch.tensor([1.0, 2.0, 4.0, 2.0], dtype=torch.float64).repeat(16)
+    o["b1"] = torch.randint(-2, 7, (64,), generator=g).double()
+    o["w2"] = _sparse(64, 64, 3, 3, g)
+    o["b2"] = torch.randint(-8, 9, (64,), generator=g).double()
+    o["w3"] = _sparse(256, 64, 1, 3, g) * 2
+    o["w3"][::32] = o["w3"][::32].abs() * 8  # (a few values reach past 448)
+    o["b3"] = torch.randint(-16, 17, (256,), generator=g).double()
+    return o
+
+
+def head_exact_operands(B, seed=1):
+    """The same for bottleneck56_head: x in 0..3, integer t1 and t2 <= 256."""
+    g = torch.Generator().manual_seed(seed)
+    o = {"x": torch.randint(0, 4, (B, 64, 56, 56), generator=g).double()}
+    o["w1"] = _sparse(64, 64, 1, 4, g)
+    o["b1"] = torch.randint(-2, 7, (64,), generator=g).double()
+    o["w2"] = _sparse(64, 64, 3, 3, g)
+    o["b2"] = torch.randint(-8, 9, (64,), generator=g).double()
+    return o
+
+
+def e4m3_bytes(v):
+    """relu(v) saturated at 448 and rounded to e4m3 (tests/_e4m3_ref.py's
+    rule: torch's fp32 -> float8_e4m3fn conversion, nearest even), as bytes.
+    v must be exact in fp32."""
+    import _e4m3_ref
+    return _e4m3_ref.round_bytes(v.clamp(0, E4M3_MAX))
+
+
 def fault_ds_missing(ref, x56, wd, b=0, frag=3):
     """The 1x1/s2 downsample's products left out of one 16-pixel fragment
     (pixels 16 frag .. 16 frag + 15 of image b, row-major) of a conv that
@@ -322,3 +554,148 @@ def prob_without_split(logits, lo, hi):
     e = (z - m).exp()
     e[:, lo:hi] = 0
     return 1.0 / e.sum(-1)
+
+
+# ---------------------------------------------------------------- conv1x1's block loop (conv1x1.hip), in matrix form
+C1_KEYS = [(False, False, False, 1), (False, False, True, 1), (False, False, False, 2), (True, False, False, 1),
+           (False, True, False, 1), (False, True, True, 1), (True, True, False, 2), (True, True, False, 1),
+           (True, True, True, 1)]  # (in8, out8, residual, stride): the launcher's switch
+C1_MSTRIDE = 8  # block stride of a workgroup on a grid of 8 workgroups per channel slice
+
+
+def c1_forms():
+    """(in8, out8, res, stride, rb) for every key and staged row class the
+    launcher takes (stride 2 stops at 512-B rows)."""
+    return [k + (rb,) for k in C1_KEYS for rb in (128, 256, 512, 1024) if not (k[3] == 2 and rb > 512)]
+
+
+def c1_operands(nblocks, in8, out8, res, stride, rb, N=256, seed=0, cin2=0):
+    """A 1x1 conv over nblocks pixel blocks (64 pixels, 32 for 1-KB rows), one
+    block an image: 8x8 outputs (16x16 inputs at stride 2), 4x8 for 1-KB rows.
+    x / x2: NHWC float64 (e4m3 codes or bf16 values); X: the [M, K] rows the
+    conv reads, in block order; w [N, K]; alpha / bias [N]; r: residual [M, N]
+    (e4m3 codes times res_scale, or bf16 values); out_scale puts the largest
+    output at 400 (e4m3 output), and is no power of two."""
+    g = torch.Generator().manual_seed(seed)
+    esz = 1 if in8 else 2
+    K = rb // esz
+    Cin = K - cin2
+    bm = 64 if rb <= 512 else 32
+    Ho, Wo = bm // 8, 8
+    o = {"in8": in8, "out8": out8, "stride": stride, "bm": bm, "S": 3 if rb <= 256 else 2, "K": K, "N": N,
+         "alpha": None, "r": None, "res_scale": 1.0, "x2": None, "out_scale": None}
+    shape = (nblocks, stride * Ho, stride * Wo)
+    if in8:
+        xv = torch.rand(*shape, Cin, generator=g) * 4
+        sx = f32(float(xv.max()) / E4M3_MAX)
+        o["x"] = (xv / sx).clamp(0, E4M3_MAX).to(torch.float8_e4m3fn).double()
+        w, sw = e4m3_weights(torch.randn(N, K, 1, 1, generator=g) / K ** 0.5)
+        o["w"], o["alpha"] = w.reshape(N, K), (sx * sw).float().double()
+    else:
+        o["x"] = torch.randn(*shape, Cin, generator=g).bfloat16().double()
+        o["w"] = (torch.randn(N, K, generator=g) / K ** 0.5).bfloat16().double()
+        if cin2:
+            o["x2"] = torch.randn(*shape, cin2, generator=g).bfloat16().double()
+    o["bias"] = (torch.randn(N, generator=g) * 0.1).float().double()
+    X = o["x"][:, ::stride, ::stride].reshape(-1, Cin)
+    o["X"] = X if not cin2 else torch.cat([X, o["x2"].reshape(-1, cin2)], 1)
+    if res:
+        rv = torch.randn(nblocks * bm, N, generator=g)
+        if out8:
+            o["res_scale"] = f32(float(rv.abs().max()) / E4M3_MAX)
+            o["r"] = (rv / o["res_scale"]).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn).double()
+        else:
+            o["r"] = rv.bfloat16().double()
+    if out8:
+        o["out_scale"] = float(torch.relu(c1_ref(o)[0]).max()) / 400.0
+    return o
+
+
+def c1_ref(o, X=None, r=None):
+    """(ref64 before the ReLU, mag), [M, N], of `c1_operands` (X / r: a
+    control's rows in their place)."""
+    X = o["X"] if X is None else X
+    r = o["r"] if r is None else r
+    v, mag = X @ o["w"].t(), X.abs() @ o["w"].abs().t()
+    if o["alpha"] is not None:
+        v, mag = v * o["alpha"], mag * o["alpha"].abs()
+    v, mag = v + o["bias"], mag + o["bias"].abs()
+    if r is not None:
+        v, mag = v + r * o["res_scale"], mag + r.abs() * o["res_scale"]
+    return v, mag
+
+
+def c1_bar(o, v, mag):
+    """(the expected output in its own units, its bar, the relative-L2 bar)."""
+    if o["out8"]:
+        inv = f32(1.0 / o["out_scale"])
+        return torch.relu(v) * inv, e4m3_bound(torch.relu(v), mag, o["K"], inv), 4e-2
+    return torch.relu(v), bound(torch.relu(v), mag, o["K"]), L2_BF16
+
+
+def _blocks(t, bm):
+    return t.reshape(-1, bm, t.shape[-1])
+
+
+def c1_controls(o):
+    """Faulty references of the block loop (before the ReLU): a stage slot
+    read before its DMA landed (block j from the rows of block j - S mstride,
+    which held the slot), and the residual of the other register set (block
+    j +- mstride's)."""
+    bm, back = o["bm"], o["S"] * C1_MSTRIDE
+    nb = o["X"].shape[0] // bm
+    out = []
+    if nb > back:
+        Xb = _blocks(o["X"], bm).clone()
+        Xb[back:] = _blocks(o["X"], bm)[:nb - back]
+        out.append(("stale stage slot", c1_ref(o, X=Xb.reshape(o["X"].shape))[0]))
+    if o["r"] is not None and nb > C1_MSTRIDE:
+        rb_ = _blocks(o["r"], bm)
+        rw = torch.cat([rb_[C1_MSTRIDE:], rb_[nb - 2 * C1_MSTRIDE:nb - C1_MSTRIDE]] if nb >= 2 * C1_MSTRIDE
+                       else [rb_[C1_MSTRIDE:], rb_[:C1_MSTRIDE]])
+        out.append(("residual of the other register set", c1_ref(o, r=rw.reshape(o["r"].shape))[0]))
+    return out
+
+
+def c1_cat_controls(o, cin):
+    """Concatenated K: x2's K block read from x, and the two K blocks swapped."""
+    X = o["X"]
+    return [("x2's K block read from x", c1_ref(o, X=torch.cat([X[:, :cin], X[:, :cin]], 1))[0]),
+            ("K blocks swapped", c1_ref(o, X=torch.cat([X[:, cin:], X[:, :cin]], 1))[0])]
+
+
+def chain_operands(nblocks, seed=0):
+    """conv1x1_chain: the expand conv (e4m3 128 -> 512, e4m3 residual) as
+    `c1_operands`, and the reduce conv on its output codes (512 -> 128 e4m3):
+    w2 codes [128, 512], alpha2 = out_scale s_w2, bias2, out_scale2 (the
+    largest y2 at 400, from the float64 y rounded to e4m3)."""
+    o = c1_operands(nblocks, True, True, True, 1, 128, N=512, seed=seed)
+    g = torch.Generator().manual_seed(seed + 1)
+    w2, s2 = e4m3_weights(torch.randn(128, 512, 1, 1, generator=g) / 512 ** 0.5)
+    o["w2"] = w2.reshape(128, 512)
+    o["alpha2"] = (f32(o["out_scale"]) * s2).float().double()
+    o["bias2"] = (torch.randn(128, generator=g) * 0.1).float().double()
+    y = (torch.relu(c1_ref(o)[0]) * f32(1.0 / o["out_scale"])).float().to(torch.float8_e4m3fn).double()
+    o["out_scale2"] = float(torch.relu(chain_reduce(o, y)[0]).max()) / 400.0
+    return o
+
+
+def chain_reduce(o, y):
+    """(ref64 before the ReLU, mag) of the reduce conv on the y codes [M, 512]."""
+    v, mag = y @ o["w2"].t() * o["alpha2"] + o["bias2"], y.abs() @ o["w2"].abs().t() * o["alpha2"].abs() + o["bias2"].abs()
+    return v, mag
+
+
+def chain_reduce_bar(o, y):
+    v, mag = chain_reduce(o, y)
+    inv = f32(1.0 / o["out_scale2"])
+    return torch.relu(v) * inv, e4m3_bound(torch.relu(v), mag, 512, inv)
+
+
+def chain_controls(o, y):
+    """y2 of block j computed from block j - mstride's y (a stale ybuf)."""
+    yb = _blocks(y, 64)
+    if yb.shape[0] <= C1_MSTRIDE:
+        return []
+    stale = torch.cat([yb[:C1_MSTRIDE], yb[:-C1_MSTRIDE]]).reshape(y.shape)
+    return [("stale ybuf", chain_reduce(o, stale)[0])]

@@ -200,3 +200,143 @@ def test_strided_and_downsample_faults():
     kb.assert_close(got, torch.relu(ref), bnd, "conv + downsample clean")
     kb.assert_rejects(got, torch.relu(kb.fault_ds_missing(ref, x56, wd, b=1, frag=48)), bnd, "ds missing")
     kb.assert_rejects(got, torch.relu(kb.fault_strided_parity(ref, x56, wd, 27, 0)), bnd, "ds parity")
+
+
+# ---------------------------------------------------------------- bottleneck56 / bottleneck56_head (kb.chain)
+BN_RING = kb.kernel_const("bottleneck56.hip", "kRing")
+
+
+def _bottleneck_fp32(o):
+    """bottleneck56 as the kernel computes it: fp32 convs, bf16 t1 / t2,
+    the last stage in the output's units (kb.bottleneck_last), e4m3 out."""
+    w3s, b3s, res = kb.bottleneck_last(o)
+    a1, b1 = o["a1"].float().view(1, -1, 1, 1), o["b1"].float().view(1, -1, 1, 1)
+    t1 = torch.relu(F.conv2d(o["x"].float(), o["w1"].float()) * a1 + b1).bfloat16().float()
+    t2 = torch.relu(F.conv2d(t1, o["w2"].float(), o["b2"].float(), 1, 1)).bfloat16().float()
+    v = F.conv2d(t2, w3s.float(), b3s.float()) + res.float()
+    return v.clamp(0, 448).to(torch.float8_e4m3fn).double()
+
+
+def _head_fp32(o):
+    t1 = torch.relu(F.conv2d(o["x"].float(), o["w1"].float(), o["b1"].float())).bfloat16().float()
+    return kb.bf16r(torch.relu(F.conv2d(t1, o["w2"].float(), o["b2"].float(), 1, 1)))
+
+
+def test_chain_is_chained():
+    """kb.chained is the two-stage case of kb.chain, and a one-stage chain is
+    the plain bar."""
+    ops5 = kb.block_operands(1, seed=6)
+    x, w1, b1, w2, b2 = ops5
+    ref, bnd, delta, t = kb.chained(*ops5)
+    r2, b2_, deltas, ts = kb.chain(x, [(w1, b1, 576, 1), (w2, b2, 576, 1)], res=x)
+    assert torch.equal(ref, r2) and torch.equal(bnd, b2_) and torch.equal(delta, deltas[0]) and torch.equal(t, ts[0])
+    v, mag = kb.conv_ref(x, w1, b1, 1, 1)
+    r1, b1_, d1, t1 = kb.chain(x, [(w1, b1, 576, 1)])
+    assert torch.equal(r1, v) and torch.equal(b1_, kb.bound(torch.relu(v), mag, 576)) and d1 == [] and t1 == []
+
+
+def test_bottleneck_bar_and_controls():
+    """The GPU bar test's own operands (test_kernels_resnet50_gpu.py: B = 2,
+    seed 156): the fp32 model passes, no control is swamped by the delta
+    terms, and the output scale is no power of two."""
+    o = kb.bottleneck_operands(2, seed=156)
+    inv = 1.0 / o["out_scale"]
+    assert torch.frexp(torch.tensor(inv, dtype=torch.float64))[0].item() != 0.5
+    w3s, _, _ = kb.bottleneck_last(o)
+    assert not torch.equal(w3s, o["w3"] * kb.f32(inv))  # the re-rounding of w3 / s_y is visible
+    ref, bnd, deltas, _ = kb.bottleneck_ref(o)
+    got = _bottleneck_fp32(o)
+    ratio, _ = kb.assert_close(got, torch.relu(ref), bnd, "bottleneck56 model", l2=4e-2)
+    share = (F.conv2d(deltas[1], w3s.abs()) / bnd).max().item()
+    ratios = [kb.worst(got, torch.relu(w), bnd)[0] for _, w in kb.bottleneck_controls(o, BN_RING)]
+    print(f"bottleneck56: delta term at most {share:.2f} of the bar, smallest control ratio {min(ratios):.1f}")
+    assert min(ratios) > 1.0, ratios
+    # without the model of the re-rounded weights the reference itself is off by more than the summation slack
+    plain = kb.conv_ref(kb.bf16r(torch.relu(kb.conv_ref(kb.bottleneck_ref(o)[3][0], o["w2"], o["b2"], 1, 1)[0])),
+                        o["w3"] * inv, o["b3"] * inv, 1, 0, res=o["x"] * o["res_scale"] * inv)[0]
+    assert (plain - ref).abs().max().item() > 64 * kb.EPS_SUM * 400
+
+
+def test_bottleneck_head_bar_and_controls():
+    o = kb.head_operands(2, seed=157)
+    ref, bnd, deltas, _ = kb.head_ref(o)
+    got = _head_fp32(o)
+    kb.assert_close(got, torch.relu(ref), bnd, "bottleneck56_head model")
+    share = (F.conv2d(deltas[0], o["w2"].abs(), None, 1, 1) / bnd).max().item()
+    ratios = [kb.worst(got, torch.relu(w), bnd)[0] for _, w in kb.head_controls(o, BN_RING)]
+    print(f"bottleneck56_head: delta term at most {share:.2f} of the bar, smallest control ratio {min(ratios):.1f}")
+    assert min(ratios) > 1.0, ratios
+
+
+@pytest.mark.parametrize("B", [1, 3])
+def test_bottleneck_exact_operands(B):
+    """The exact-integer test's conditions, on the reference alone: both
+    intermediates are integers that bf16 holds, every weight tap and input
+    channel is used, the output has negatives, grid ties and a few values
+    past 448, and every control changes at least one expected byte."""
+    o = kb.bottleneck_exact_operands(B)
+    ref, _, _, (t1, t2) = kb.bottleneck_ref(o, bar=False)
+    for t in (t1, t2):
+        assert torch.equal(kb.bf16r(t), t) and torch.equal(t, t.round()) and float(t.max()) <= 256
+    w3s, b3s, _ = kb.bottleneck_last(o)
+    assert torch.equal(w3s, o["w3"] / o["out_scale"]) and torch.equal(ref.float().double(), ref)
+    assert float(o["b1"].max()) >= 4 and len(set(o["a1"].tolist())) == 3
+    assert bool((o["x"] != 0).all())
+    for w in (o["w1"], o["w2"], o["w3"]):
+        assert bool((w.abs().sum((0, 2, 3)) > 0).all()) and bool((w.abs().sum((0, 1)) > 0).all())
+        assert bool((w.abs().sum((1, 2, 3)) > 0).all()) and torch.equal(w, w.round())
+    over = int((ref > 448).sum())
+    assert bool((ref < 0).any()) and 0 < over < ref.numel() // 100
+    assert bool((ref[(ref > 16) & (ref < 32)] % 2 == 1).any())  # ties of the e4m3 grid (step 2 in [16, 32))
+    want = kb.e4m3_bytes(ref)
+    for name, wrong in kb.bottleneck_controls(o, BN_RING):
+        assert not torch.equal(kb.e4m3_bytes(wrong), want), name
+
+
+@pytest.mark.parametrize("B", [1, 3])
+def test_head_exact_operands(B):
+    o = kb.head_exact_operands(B)
+    ref, _, _, (t1,) = kb.head_ref(o)
+    t2 = torch.relu(ref)
+    for t in (t1, t2):
+        assert torch.equal(kb.bf16r(t), t) and torch.equal(t, t.round()) and float(t.max()) <= 256
+    assert bool((ref < 0).any()) and float(o["b1"].max()) >= 4
+    for w in (o["w1"], o["w2"]):
+        assert bool((w.abs().sum((0, 2, 3)) > 0).all()) and bool((w.abs().sum((0, 1)) > 0).all())
+        assert bool((w.abs().sum((1, 2, 3)) > 0).all())
+    for name, wrong in kb.head_controls(o, BN_RING):
+        assert not torch.equal(torch.relu(wrong), t2), name
+
+
+@pytest.mark.parametrize("form", [(True, True, True, 1, 128), (False, False, True, 1, 512), (True, False, False, 1, 1024),
+                                  (False, True, False, 1, 256), (True, True, False, 2, 256)])
+def test_conv1x1_block_loop_controls(form):
+    """conv1x1's block-loop controls on the GPU test's operands (43 blocks):
+    the reference rounded as the kernel rounds passes, a stale stage slot and
+    the other register set's residual do not."""
+    o = kb.c1_operands(43, *form, seed=300 + kb.c1_forms().index(form))
+    v, mag = kb.c1_ref(o)
+    want, bnd, l2 = kb.c1_bar(o, v, mag)
+    got = want.float().to(torch.float8_e4m3fn).double() if o["out8"] else kb.bf16r(want)
+    kb.assert_close(got, want, bnd, "clean", l2=l2)
+    controls = kb.c1_controls(o)
+    assert len(controls) == (2 if form[2] else 1)
+    for name, wrong in controls:
+        kb.assert_rejects(got, kb.c1_bar(o, wrong, mag)[0], bnd, name)
+
+
+def test_conv1x1_chain_and_concat_controls():
+    o = kb.chain_operands(43, seed=360 + 43)
+    v, mag = kb.c1_ref(o)
+    want, bnd, _ = kb.c1_bar(o, v, mag)
+    y = want.float().to(torch.float8_e4m3fn).double()
+    want2, bnd2 = kb.chain_reduce_bar(o, y)
+    y2 = want2.float().to(torch.float8_e4m3fn).double()
+    kb.assert_close(y2, want2, bnd2, "chain y2", l2=4e-2)
+    for name, wrong in kb.chain_controls(o, y):
+        kb.assert_rejects(y2, torch.relu(wrong) * kb.f32(1.0 / o["out_scale2"]), bnd2, name)
+    o = kb.c1_operands(43, False, False, False, 1, 256, seed=350 + 43, cin2=64)
+    v, mag = kb.c1_ref(o)
+    want, bnd, _ = kb.c1_bar(o, v, mag)
+    for name, wrong in kb.c1_cat_controls(o, 64):
+        kb.assert_rejects(kb.bf16r(want), torch.relu(wrong), bnd, name)

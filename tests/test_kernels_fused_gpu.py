@@ -19,8 +19,8 @@ head_fused 0.08, 3.3e-3 (e4m3 input 0.04); head_pooled < 0.001, 2.8e-7 (its
 input is already bf16). The weakest negative control sits at 1.9 times the
 bar (the stream conv's pool with its last pixel left out).
 
-ResNet50's layer1 kernels (bottleneck56_head, bottleneck56) are not covered
-here.
+ResNet50's layer1 kernels (bottleneck56_head, bottleneck56), conv1x1's block
+loop and conv1x1_chain have theirs in test_kernels_resnet50_gpu.py.
 """
 import pytest
 import torch

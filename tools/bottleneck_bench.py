@@ -2,7 +2,7 @@
 """Microbenchmark of the fused ResNet50 layer1 bottleneck (bottleneck56.hip)
 at B=256: event-timed, median over --iters event pairs of --reps launches
 each (its phase knock-outs: profiles/r3_bottleneck_*.txt). Random operands
-(timing only; numerics are tests/test_engine_gpu.py's)."""
+(timing only; numerics are tests/test_kernels_resnet50_gpu.py's)."""
 import argparse
 import os
 import statistics
