@@ -82,11 +82,12 @@ def stem_image(x_nhwc3: torch.Tensor, pad: int, row_width: int) -> torch.Tensor:
 
 
 def fc(x: torch.Tensor, w_packed: torch.Tensor, cout: int, bias: torch.Tensor | None = None, relu: bool = False,
-       out_f32: bool = False, splits: int = 0) -> torch.Tensor:
+       out_f32: bool = False, splits: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
     """Fully connected layer at M <= 256 rows on fc_gemm.hip: x bf16 [M, K]
     (K = w_packed.shape[1], a multiple of 64), w_packed [Npad, K] (Npad % 128
     == 0) -> [M, cout] bf16 (fp32 with out_f32). splits: K slices (0: the
-    engine's choice), fp32 partials reduced with the bias and ReLU."""
+    engine's choice), fp32 partials reduced with the bias and ReLU. ``out``:
+    the [M, cout] tensor to write."""
     _need_cuda(x, w_packed, bias)
     C = native()
     M, K = x.shape
@@ -96,7 +97,9 @@ def fc(x: torch.Tensor, w_packed: torch.Tensor, cout: int, bias: torch.Tensor | 
         splits = C.fc_gemm_splits(M, K, w_packed.shape[0], torch.cuda.get_device_properties(x.device).multi_processor_count)
     ws = torch.empty(splits * M * w_packed.shape[0], device=x.device, dtype=torch.float32)
     return conv2d(x.contiguous().view(M, 1, 1, K), w_packed, cout, 1, 1, bias=bias, relu=relu, out_f32=out_f32,
-                  split_k=splits, tile=C.CONV_FC, ws=ws).view(M, cout)
+                  split_k=splits, tile=C.CONV_FC, ws=ws,
+                  out=None if out is None else _out_tensor(out, (M, cout), torch.float32 if out_f32 else
+                                                           torch.bfloat16, x.device, "fc")).view(M, cout)
 
 
 def conv2d(x: torch.Tensor, w_packed: torch.Tensor, cout: int, kh: int, kw: int, stride: int = 1,
@@ -459,12 +462,13 @@ def conv2d_fp8(x: torch.Tensor, w_q: torch.Tensor, alpha: torch.Tensor, cout: in
                stride: int = 1, pad: int = 0, bias: torch.Tensor | None = None, res: torch.Tensor | None = None,
                res_scale: float = 1.0, relu: bool = False, out_scale: float | None = None,
                tile: int = -1, out: torch.Tensor | None = None, num_cus: int = 0,
-               x2: torch.Tensor | None = None) -> torch.Tensor:
+               x2: torch.Tensor | None = None, max_blocks: int = 0) -> torch.Tensor:
     """fp8 implicit-GEMM conv (block-scaled e4m3 MFMA). x: e4m3 NHWC
     (Cin % 128 == 0) or bf16 (then w_q is bf16-packed and alpha unused).
     alpha = s_x * s_w[n]; residual e4m3 scaled by res_scale; output e4m3
     with scale out_scale (or bf16 when out_scale is None). ``out``: the
-    output tensor to write; ``num_cus`` / ``x2``: as for ``conv2d``."""
+    output tensor to write; ``num_cus`` / ``x2`` / ``max_blocks``: as for
+    ``conv2d``."""
     _need_cuda(x, w_q, alpha, bias, res, out, x2)
     C = native()
     B, H, W, Cin = x.shape
@@ -480,7 +484,7 @@ def conv2d_fp8(x: torch.Tensor, w_q: torch.Tensor, alpha: torch.Tensor, cout: in
     C.conv2d(x=_ptr(x.contiguous()), w=_ptr(w_q), bias=_ptr(bias), res=_ptr(res), y=_ptr(y), B=B, H=H, W=W, Cin=Cin,
              KH=kh, KW=kw, stride=stride, pad=pad, N=cout, Npad=w_q.shape[0], Kpad=w_q.shape[1], ldo=cout,
              relu=relu, out_f32=False, split_k=1, ws=0, tile=tile, zero=_ptr(_zero_page(x.device)), stem=False,
-             Ho=Ho, Wo=Wo, max_blocks=0, stream=_stream(), in_fp8=in8, out_fp8=out8, alpha=_ptr(al),
+             Ho=Ho, Wo=Wo, max_blocks=max_blocks, stream=_stream(), in_fp8=in8, out_fp8=out8, alpha=_ptr(al),
              res_scale=res_scale, out_inv_scale=(1.0 / out_scale) if out8 else 1.0, num_cus=num_cus,
              x2=_ptr(None if x2 is None else _second_input(x, x2)), cin2=0 if x2 is None else x2.shape[-1])
     return y

@@ -1,6 +1,6 @@
 """The element-wise bar of the op tests (test_kernels_fused_gpu.py,
 test_kernels_resnet_gpu.py, test_kernels_resnet50_gpu.py,
-test_kernel_bar_cpu.py): a kernel's output against
+test_kernels_gemm_gpu.py, test_kernel_bar_cpu.py): a kernel's output against
 the float64 result on the same bf16-rounded operands.
 
 A rounding argument, not a measurement. A bf16-output conv or fc with K
@@ -62,7 +62,11 @@ a zero padding selects (every window holds a value >= 0).
 Measured on an MI355X: the worst |err| / bar of any kernel is 0.99 (the 1x1
 downsample outputs, K = 64; alex_stem 0.95), per kernel in the docstrings of
 test_kernels_fused_gpu.py, test_kernels_resnet_gpu.py and
-test_kernels_resnet50_gpu.py.
+test_kernels_resnet50_gpu.py. The general matrix family
+(test_kernels_gemm_gpu.py): conv_igemm 0.94 over its 11 tiles, 0.44 with
+split-K, 0.77 persistent, 0.97 the stem, 0.91 / 0.94 / 0.59 the e4m3 in / out,
+bf16 in / e4m3 out and e4m3 in / bf16 out forms; conv_bigtile 0.82 with slabs,
+0.81 persistent; fc_gemm 0.90; every fp32 output below 0.01.
 
 Next to the bar every test keeps the project's relative-L2 bar for bf16
 outputs (5e-3), and a negative control: a reference with one realistic kernel
@@ -699,3 +703,320 @@ def chain_controls(o, y):
         return []
     stale = torch.cat([yb[:C1_MSTRIDE], yb[:-C1_MSTRIDE]]).reshape(y.shape)
     return [("stale ybuf", chain_reduce(o, stale)[0])]
+
+
+# ---------------------------------------------------------------- the general matrix family
+# conv_igemm.hip's tiles 0..10, conv_bigtile.hip's 11 / 12 (slabs) and 13 (persistent): (BM, BN)
+GEMM_TILES = {0: (128, 128), 1: (256, 64), 2: (64, 256), 3: (128, 128), 4: (256, 64), 5: (64, 256), 6: (128, 128),
+              7: (128, 64), 8: (64, 128), 9: (128, 64), 10: (64, 128), 11: (256, 256), 12: (256, 128), 13: (256, 128)}
+L2_E4M3 = 4e-2
+
+
+def npad(n):
+    """conv_igemm.hip's conv_npad."""
+    return 64 if n <= 64 else n if n % 64 == 0 else (n + 127) // 128 * 128
+
+
+def rows(t):
+    """NCHW -> the GEMM's [M, N] (m = (b Ho + ho) Wo + wo)."""
+    return nhwc(t).reshape(-1, t.shape[1])
+
+
+def unrows(r, like):
+    B, C, H, W = like.shape
+    return nchw(r.reshape(B, H, W, C))
+
+
+def igemm_slices(k_tiles, split_k):
+    """K-tile ranges of conv2d_igemm's slices: ceil(k_tiles / split_k) tiles
+    each, so fewer slices than asked for when that does not come out even
+    (72 K tiles at split_k = 13: 12 slices of 6)."""
+    per = -(-k_tiles // max(1, split_k))
+    return [(t, min(k_tiles, t + per)) for t in range(0, k_tiles, per)]
+
+
+def bigtile_slices(k_tiles, splits):
+    """conv_bt_kernel's: slice s = K tiles [k_tiles s / splits, k_tiles (s + 1) / splits)."""
+    return [(k_tiles * s // splits, k_tiles * (s + 1) // splits) for s in range(splits)]
+
+
+_GEMM_OPERANDS = {}
+
+
+def gemm_operands(B, H, W, Cin, Cout, k, stride, pad, res=False, seed=0, exact=False, in8=False, out8=False):
+    """A conv of the matrix family, NCHW float64 (made once per argument set
+    and shared: do not modify). bf16 values, or with in8 e4m3 codes x >= 0 and
+    w with alpha = s_x s_w; res: bf16 values, with out8 e4m3 codes times
+    res_scale; out8: out_scale puts the largest output at 400 of 448 and is
+    no power of two. Cin = 3: a stem (K = 3 k k).
+
+    exact: integers for which every fp32 partial sum, the bias and residual
+    adds and the scalings are exact in any order: x in -3..3 (codes 0..3), 6
+    weights of +-1 / +-2 per output channel, alpha in {1, 2, 4}, biases and
+    residual in -8..8 (res_scale 4), out_scale 2; |v| <= 160, integers, exact
+    in bf16. With out8 every 32nd channel's bias is raised by 2000: those
+    outputs saturate at 448."""
+    key = (B, H, W, Cin, Cout, k, stride, pad, res, seed, exact, in8, out8)
+    if key in _GEMM_OPERANDS:
+        return _GEMM_OPERANDS[key]
+    g = torch.Generator().manual_seed(seed)
+    K = Cin * k * k
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    o = {"stride": stride, "pad": pad, "k": k, "K": K, "N": Cout, "in8": in8, "out8": out8, "alpha": None, "r": None,
+         "res_scale": 1.0, "out_scale": None, "bk": 128 if in8 else 64, "stem": Cin == 3}
+    if exact:
+        o["x"] = torch.randint(0 if in8 else -3, 4, (B, Cin, H, W), generator=g).double()
+        o["w"] = _sparse(Cout, Cin, k, 6, g)
+        if in8:
+            o["alpha"] = torch.tensor([1.0, 2.0, 4.0, 2.0], dtype=torch.float64).repeat(Cout // 4)
+        o["bias"] = torch.randint(-8, 9, (Cout,), generator=g).double()
+        if out8:
+            o["bias"][::32] += 2000
+            o["out_scale"] = 2.0
+        if res:
+            o["r"] = torch.randint(-8, 9, (B, Cout, Ho, Wo), generator=g).double()
+            o["res_scale"] = 4.0 if out8 else 1.0
+    else:
+        if in8:
+            xv = torch.rand(B, Cin, H, W, generator=g) * 4
+            sx = f32(float(xv.max()) / E4M3_MAX)
+            o["x"] = (xv / sx).clamp(0, E4M3_MAX).to(torch.float8_e4m3fn).double()
+            o["w"], sw = e4m3_weights(torch.randn(Cout, Cin, k, k, generator=g) / K ** 0.5)
+            o["alpha"] = (sx * sw).float().double()
+        else:
+            o["x"] = torch.randn(B, Cin, H, W, generator=g).bfloat16().double()
+            o["w"] = (torch.randn(Cout, Cin, k, k, generator=g) / K ** 0.5).bfloat16().double()
+        o["bias"] = (torch.randn(Cout, generator=g) * 0.1).float().double()
+        if res:
+            rv = torch.randn(B, Cout, Ho, Wo, generator=g)
+            if out8:
+                o["res_scale"] = f32(float(rv.abs().max()) / E4M3_MAX)
+                o["r"] = (rv / o["res_scale"]).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn).double()
+            else:
+                o["r"] = rv.bfloat16().double()
+        if out8:
+            o["out_scale"] = float(torch.relu(gemm_ref(o)[0]).max()) / 400.0
+    o["ref"] = gemm_ref(o)
+    _GEMM_OPERANDS[key] = o
+    return o
+
+
+def gemm_ref(o):
+    """(ref64 before the ReLU, mag), NCHW: conv(x, w) (alpha) + bias (+ r res_scale)."""
+    x, w, s, p = o["x"], o["w"], o["stride"], o["pad"]
+    v, mag = F.conv2d(x, w, None, s, p), F.conv2d(x.abs(), w.abs(), None, s, p)
+    bias = o["bias"].view(1, -1, 1, 1)
+    if o["alpha"] is not None:
+        a = o["alpha"].view(1, -1, 1, 1)
+        v, mag = v * a, mag * a.abs()
+    v, mag = v + bias, mag + bias.abs()
+    if o["r"] is not None:
+        v, mag = v + o["r"] * o["res_scale"], mag + o["r"].abs() * o["res_scale"]
+    return v, mag
+
+
+def gemm_k_range(o, t0, t1):
+    """What K tiles t0..t1-1 (o["bk"] wide, k = (kh KW + kw) Cin + c) add to
+    the output, NCHW float64."""
+    w = o["w"]
+    wk = torch.zeros_like(w).permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+    lo, hi = t0 * o["bk"], t1 * o["bk"]
+    wk[:, lo:hi] = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)[:, lo:hi]
+    wk = wk.reshape(w.shape[0], w.shape[2], w.shape[3], w.shape[1]).permute(0, 3, 1, 2)
+    v = F.conv2d(o["x"], wk, None, o["stride"], o["pad"])
+    return v if o["alpha"] is None else v * o["alpha"].view(1, -1, 1, 1)
+
+
+def gemm_bar(o, v, mag, out_f32=False):
+    """(the expected output in its own units, its bar, the relative-L2 bar)
+    of a reference v (before the ReLU) with the operands' mag."""
+    if o["out8"]:
+        inv = f32(1.0 / o["out_scale"])
+        return torch.relu(v) * inv, e4m3_bound(torch.relu(v), mag, o["K"], inv), L2_E4M3
+    return torch.relu(v), bound(torch.relu(v), mag, o["K"], out_bf16=not out_f32), L2_BF16
+
+
+def gemm_rounded(o, v, out_f32=False):
+    """The float64 reference rounded to the output type: what an ideal kernel gives."""
+    if o["out8"]:
+        return (torch.relu(v) * f32(1.0 / o["out_scale"])).float().to(torch.float8_e4m3fn).double()
+    return torch.relu(v).float().double() if out_f32 else bf16r(torch.relu(v))
+
+
+def fault_tail_tile(R, bm):
+    """An unclamped row index: the rows of the last, partial M tile ([M, N]
+    rows, M % bm of them) take the previous tile's rows at the same offset."""
+    M = R.shape[0]
+    t = M % bm
+    assert t and M > bm, (M, bm)
+    out = R.clone()
+    out[M - t:] = R[M - t - bm:M - bm]
+    return out
+
+
+def fault_k_tile_missing(R, lost, m0, bm, n0=0, bn=None):
+    """One K tile's products (`lost`, [M, N]) left out of the M tile at row
+    m0 (and of the N tile at column n0, if bn is given): a stage of the LDS
+    ring consumed before it landed, or a slice's last K tile dropped."""
+    out = R.clone()
+    n1 = R.shape[1] if bn is None else n0 + bn
+    out[m0:m0 + bm, n0:n1] -= lost[m0:m0 + bm, n0:n1]
+    return out
+
+
+def fault_slice_missing(R, lost, m0, bm, n0, bn):
+    """One split-K slice (`lost`: its products, [M, N]) left out of the
+    reduction for the output tile at (m0, n0): a slab that was not handed
+    off, or the reduce loop's 8 / 4 / 1 remainder skipping a slice."""
+    return fault_k_tile_missing(R, lost, m0, bm, n0, bn)
+
+
+def fault_pad_columns(R, n_pad, row):
+    """Rows of ldo == N with N < Npad: row `row - 1`'s pad columns N..Npad-1
+    (zeros: zero weights, zero bias) land on row `row`'s first columns."""
+    N = R.shape[1]
+    assert n_pad > N and row >= 1
+    out = R.clone()
+    out[row, :n_pad - N] = 0
+    return out
+
+
+def gemm_controls(o, bm, bn, slices=None):
+    """Faulty references (NCHW, before the ReLU) of a conv of the matrix
+    family on (bm, bn) tiles with the split-K `slices` (K-tile ranges): a chunk
+    swap at the last pixel of the last image, a batch shift, the partial last M
+    tile, the last K tile missing from the last full M tile, the last slice
+    missing from the tile at (0, last N tile), and pad columns spilling into
+    the second M tile's first row."""
+    v = o["ref"][0]
+    B, N, Ho, Wo = v.shape
+    M, R = B * Ho * Wo, rows(v)
+    out = [("chunk swap", fault_chunk_swap(v, b=B - 1, h=Ho - 1, w=Wo - 2, chunk=1, width=16 if o["out8"] else 8))]
+    if B > 1:
+        out.append(("batch shift", fault_batch_shift(v)))
+    if M > bm and M % bm:
+        out.append(("tail tile", unrows(fault_tail_tile(R, bm), v)))
+    if not o["stem"]:
+        kt = o["K"] // o["bk"]
+        m0 = max(0, M // bm - 1) * bm
+        out.append(("K tile missing", unrows(fault_k_tile_missing(R, rows(gemm_k_range(o, kt - 1, kt)), m0, bm), v)))
+        if slices is not None and len(slices) > 1:
+            n0 = (npad(N) // bn - 1) * bn
+            lost = rows(gemm_k_range(o, *slices[-1]))
+            out.append(("slice missing", unrows(fault_slice_missing(R, lost, 0, bm, n0, bn), v)))
+    if N < npad(N) and M > bm:
+        out.append(("pad columns", unrows(fault_pad_columns(R, npad(N), bm), v)))
+    return out
+
+
+# The cases of tests/test_kernels_gemm_gpu.py (test_kernel_bar_cpu.py checks the
+# bar and every control on the same operands without a GPU).
+# (name, (B, H, W, Cin, Cout, k, stride, pad), res, tile, split_k, max_blocks, out_f32)
+_BASE = (3, 13, 13, 64)
+IGEMM_CASES = [("base tile %d" % t, _BASE + (512 if GEMM_TILES[t][1] == 256 else 256, 3, 1, 1), True, t, 1, 0, False)
+               for t in range(11)]
+IGEMM_CASES += [
+    ("stride 2 tile 0", (3, 13, 13, 128, 256, 3, 2, 1), False, 0, 1, 0, False),
+    ("stride 2 tile 7", (3, 13, 13, 128, 256, 3, 2, 1), False, 7, 1, 0, False),
+    ("5x5 tile 1", (2, 27, 27, 64, 192, 5, 1, 2), False, 1, 1, 0, False),
+    ("1x1 tile 0", (3, 14, 14, 512, 256, 1, 1, 0), False, 0, 1, 0, False),
+    ("1x1 tile 4", (3, 14, 14, 512, 256, 1, 1, 0), True, 4, 1, 0, False),
+    ("Cout 100 tile 0", _BASE + (100, 3, 1, 1), True, 0, 1, 0, False),
+    ("Cout 100 tile 7", _BASE + (100, 3, 1, 1), True, 7, 1, 0, False),
+]
+# 72 K tiles: split_k 2 -> 2 slices, 5 -> 5 (15 15 15 15 12), 13 -> 12 of 6 (the reduce's 8- and 4-wide loops),
+# 15 -> 15 of 5, the last of 2 (8 + 4 + 3: all three loops), 32 -> 24 of 3
+IGEMM_CASES += [("split-K %d tile %d%s" % (s, t, " f32" if f else ""), (1, 7, 7, 512, 512, 3, 1, 1), True, t, s, 0, f)
+                for t in (3, 5) for s, f in ((2, False), (5, False), (13, False), (15, False), (32, False), (13, True))]
+# tile 2 (BN = 256) cannot take Npad = 384: its case runs at Cout = 512
+IGEMM_CASES += [("persistent tile %d" % t, (5, 13, 13, 192, 512 if t == 2 else 384, 3, 1, 1), True, t, 1, 8, False)
+                for t in (0, 1, 2, 7, 8)]
+IGEMM_EXACT = [c for c in IGEMM_CASES if c[0].startswith("base") or c[0] in ("split-K 13 tile 3", "split-K 15 tile 5",
+                                                                            "persistent tile 0")]
+STEM_CASES = [(7, 2, 3), (11, 4, 2)]  # (k, stride, pad) at B = 2, hw (57, 61), 64 channels (tile 1)
+STEM_HW = (57, 61)
+
+# (name, shape, in8, out8, res, tile[, max_blocks]): conv2d_igemm's six e4m3 instantiations,
+# and the e4m3 in / out form on a persistent grid of 8 blocks (21 and 24 tiles)
+E4M3_CASES = [
+    ("e4m3 in/out persistent 128x128", (5, 13, 13, 256, 384, 3, 1, 1), True, True, True, -1, 8),
+    ("e4m3 in/out persistent 256x64", (5, 13, 13, 256, 384, 3, 1, 1), True, True, True, 1, 8),
+    ("e4m3 in/out 128x128", (2, 14, 14, 256, 256, 3, 1, 1), True, True, True, -1),
+    ("e4m3 in/out 256x64", (2, 14, 14, 256, 192, 3, 1, 1), True, True, True, 1),
+    ("bf16 in e4m3 out 128x128", (2, 14, 14, 64, 256, 1, 1, 0), False, True, False, -1),
+    ("bf16 in e4m3 out 256x64", (2, 14, 14, 64, 192, 1, 1, 0), False, True, False, 1),
+    ("e4m3 in bf16 out 128x128", (2, 14, 14, 256, 256, 3, 1, 1), True, False, True, -1),
+    ("e4m3 in bf16 out 256x64", (2, 14, 14, 256, 192, 3, 1, 1), True, False, False, 1),
+]
+
+# (name, shape, res, tile, splits or the persistent grid)
+_BT = (2, 13, 13, 128)
+BIGTILE_CASES = [("cfg 0 splits %d" % s, _BT + (512, 3, 1, 1), True, 11, s) for s in (1, 2, 5)]
+BIGTILE_CASES += [("cfg 1 splits %d" % s, _BT + (128, 3, 1, 1), True, 12, s) for s in (1, 2)]
+BIGTILE_CASES += [("stride 2 splits 2", (4, 14, 14, 256, 512, 3, 2, 1), False, 11, 2)]
+BIGTILE_CASES += [("persistent %s grid %d" % (n, g), sh, True, 13, g)
+                  for n, sh in (("28x28", (3, 28, 28, 128, 128, 3, 1, 1)), ("13x13", (5, 13, 13, 192, 384, 3, 1, 1)))
+                  for g in (1, 3)]
+BIGTILE_EXACT = [c for c in BIGTILE_CASES if c[0] in ("cfg 0 splits 5", "cfg 1 splits 2", "persistent 13x13 grid 1")]
+
+
+def gemm_case_operands(shape, res, seed, exact=False, in8=False, out8=False):
+    return gemm_operands(*shape, res=res, seed=seed, exact=exact, in8=in8, out8=out8)
+
+
+def case_seed(cases, name):
+    """Cases of one shape share their operands (and the float64 reference)."""
+    key = [c[1:3] for c in cases if c[0] == name][0]
+    return 500 + [c[1:3] for c in cases].index(key)
+
+
+# ---------------------------------------------------------------- fc_gemm.hip
+FC_KB = 64      # K block
+FC_RING = 3     # LDS slots
+FC_BN = 128     # columns per workgroup
+FC_MS, FC_NS, FC_K = (1, 17, 200, 256), (256, 1000), 1024
+_FC_OPERANDS = {}
+
+
+def fc_operands(M, K, N, seed, exact=False):
+    """x [M, K], w [N, K], bias [N] float64 (bf16 values; exact: integers as
+    for `gemm_operands`), and "ref": (ref64 before the ReLU, mag)."""
+    key = (M, K, N, seed, exact)
+    if key in _FC_OPERANDS:
+        return _FC_OPERANDS[key]
+    g = torch.Generator().manual_seed(seed)
+    if exact:
+        x = torch.randint(-3, 4, (M, K), generator=g).double()
+        w = _sparse(N, K, 1, 6, g).reshape(N, K)
+        bias = torch.randint(-8, 9, (N,), generator=g).double()
+    else:
+        x = torch.randn(M, K, generator=g).bfloat16().double()
+        w = (torch.randn(N, K, generator=g) / K ** 0.5).bfloat16().double()
+        bias = (torch.randn(N, generator=g) * 0.1).float().double()
+    o = {"x": x, "w": w, "bias": bias, "K": K, "ref": fc_ref(x, w, bias)}
+    _FC_OPERANDS[key] = o
+    return o
+
+
+def fc_controls(o, splits):
+    """Faulty references [M, N] of fc_gemm: K block 3 of the last slice read
+    from block 0's slot (ring distance 3: block 0's rows still there) for the
+    first 128 columns, the last slice missing from the last column group, rows
+    16..31 taking rows 0..15."""
+    x, w, K = o["x"], o["w"], o["K"]
+    R = o["ref"][0]
+    M, N = R.shape
+    per = K // splits
+    assert per // FC_KB > FC_RING
+    k0 = K - per
+    j, i = k0 + FC_RING * FC_KB, k0
+    stale = (x[:, i:i + FC_KB] - x[:, j:j + FC_KB]) @ w[:, j:j + FC_KB].t()
+    out = [("stale ring slot", fault_k_tile_missing(R, -stale, 0, M, 0, FC_BN))]
+    if splits > 1:
+        n0 = (N - 1) // FC_BN * FC_BN
+        out.append(("slice missing", fault_slice_missing(R, x[:, k0:] @ w[:, k0:].t(), 0, M, n0, FC_BN)))
+    if M > 16:
+        s = R.clone()
+        s[16:min(32, M)] = R[:min(32, M) - 16]
+        out.append(("row group shift", s))
+    return out

@@ -1,6 +1,8 @@
 """The op tests' bar (tests/_kernel_bar.py) on the CPU: the float64 reference
 rounded to bf16 (what a correct kernel may return at worst, to first order)
 passes against itself, and each modelled kernel fault is rejected."""
+import math
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -340,3 +342,136 @@ def test_conv1x1_chain_and_concat_controls():
     want, bnd, _ = kb.c1_bar(o, v, mag)
     for name, wrong in kb.c1_cat_controls(o, 64):
         kb.assert_rejects(kb.bf16r(want), torch.relu(wrong), bnd, name)
+
+
+# ---------------------------------------------------------------- the general matrix family (test_kernels_gemm_gpu.py)
+def _gemm_bar_and_controls(o, controls, out_f32=False, need=()):
+    """The float64 reference rounded to the output type meets the bar against
+    the true reference and misses it against every faulty one."""
+    v, mag = o["ref"]
+    want, bnd, l2 = kb.gemm_bar(o, v, mag, out_f32)
+    got = kb.gemm_rounded(o, v, out_f32)
+    kb.assert_close(got, want, bnd, "rounded reference", l2=l2)
+    names = [n for n, _ in controls]
+    assert all(n in names for n in need), (names, need)
+    for name, wrong in controls:
+        kb.assert_rejects(got, kb.gemm_bar(o, wrong, mag, out_f32)[0], bnd, name)
+
+
+def _distinct(cases, key):
+    seen, out = set(), []
+    for c in cases:
+        if key(c) not in seen:
+            seen.add(key(c))
+            out.append(c)
+    return out
+
+
+_IGEMM_DISTINCT = _distinct(kb.IGEMM_CASES, lambda c: (c[1], c[2], kb.GEMM_TILES[c[3]], c[4], c[6]))
+
+
+@pytest.mark.parametrize("case", _IGEMM_DISTINCT, ids=[c[0] for c in _IGEMM_DISTINCT])
+def test_igemm_bar_and_controls(case):
+    name, shape, res, tile, split_k, max_blocks, out_f32 = case
+    o = kb.gemm_case_operands(shape, res, kb.case_seed(kb.IGEMM_CASES, name))
+    slices = kb.igemm_slices(o["K"] // 64, split_k)
+    M = shape[0] * o["ref"][0].shape[2] * o["ref"][0].shape[3]
+    need = ["chunk swap", "K tile missing"] + (["slice missing"] if split_k > 1 else ["batch shift", "tail tile"])
+    if shape[4] == 100:
+        need.append("pad columns")
+    assert split_k > 1 or M % kb.GEMM_TILES[tile][0]
+    _gemm_bar_and_controls(o, kb.gemm_controls(o, *kb.GEMM_TILES[tile], slices), out_f32, need)
+
+
+def test_igemm_slices():
+    """conv2d_igemm's slice ranges: which split_k reaches which loop of the reduce."""
+    assert [len(kb.igemm_slices(72, s)) for s in (2, 5, 13, 15, 32)] == [2, 5, 12, 15, 24]
+    assert kb.igemm_slices(72, 5)[-1] == (60, 72) and kb.igemm_slices(72, 15)[-1] == (70, 72)
+    assert kb.bigtile_slices(18, 5) == [(0, 3), (3, 7), (7, 10), (10, 14), (14, 18)]
+    for n in (64, 100, 192, 256, 1000):
+        assert kb.npad(n) == {64: 64, 100: 128, 192: 192, 256: 256, 1000: 1024}[n]
+
+
+@pytest.mark.parametrize("k,s,p", kb.STEM_CASES)
+def test_stem_bar_and_controls(k, s, p):
+    o = kb.gemm_operands(2, *kb.STEM_HW, 3, 64, k, s, p, seed=490 + k)
+    _gemm_bar_and_controls(o, kb.gemm_controls(o, 256, 64), need=["chunk swap", "batch shift", "tail tile"])
+
+
+@pytest.mark.parametrize("case", kb.E4M3_CASES, ids=[c[0] for c in kb.E4M3_CASES])
+def test_igemm_e4m3_bar_and_controls(case):
+    name, shape, in8, out8, res, tile = case[:6]
+    o = kb.gemm_case_operands(shape, res, kb.case_seed(kb.E4M3_CASES, name), in8=in8, out8=out8)
+    bm, bn = (256, 64) if tile == 1 else (128, 128)
+    if out8:
+        top = float((torch.relu(o["ref"][0]) * kb.f32(1.0 / o["out_scale"])).max())
+        assert abs(top - 400.0) < 1e-3 and o["out_scale"] != 2.0 ** round(math.log2(o["out_scale"]))
+    _gemm_bar_and_controls(o, kb.gemm_controls(o, bm, bn),
+                           need=["chunk swap", "batch shift", "tail tile", "K tile missing"])
+
+
+@pytest.mark.parametrize("case", kb.BIGTILE_CASES, ids=[c[0] for c in kb.BIGTILE_CASES])
+def test_bigtile_bar_and_controls(case):
+    name, shape, res, tile, n = case
+    o = kb.gemm_case_operands(shape, res, kb.case_seed(kb.BIGTILE_CASES, name))
+    slices = kb.bigtile_slices(o["K"] // 64, n) if tile != 13 else None
+    need = ["chunk swap", "batch shift", "K tile missing"]
+    need += ["slice missing"] if tile != 13 and n > 1 else []
+    need += ["tail tile"] if "stride 2" not in name else []
+    _gemm_bar_and_controls(o, kb.gemm_controls(o, *kb.GEMM_TILES[tile], slices), need=need)
+
+
+_EXACT = [(c[1], c[2], False, False, kb.case_seed(kb.IGEMM_CASES, c[0])) for c in kb.IGEMM_EXACT] + \
+         [(c[1], c[4], c[2], c[3], kb.case_seed(kb.E4M3_CASES, c[0])) for c in kb.E4M3_CASES] + \
+         [(c[1], c[2], False, False, kb.case_seed(kb.BIGTILE_CASES, c[0])) for c in kb.BIGTILE_EXACT] + \
+         [((2,) + kb.STEM_HW + (3, 64, 7, 2, 3), False, False, False, 497)]
+_EXACT = _distinct(_EXACT, lambda c: c)
+
+
+@pytest.mark.parametrize("case", _EXACT, ids=[str(c) for c in _EXACT])
+def test_gemm_exact_operands(case):
+    """The exactness conditions of the integer operands: integer values small
+    enough that any fp32 partial sum is exact (sum |x| |w| alpha < 2^24),
+    outputs exact in bf16 (|v| <= 256) or in the e4m3 units' fp32, and a
+    chunk swap, a batch shift and a missing K tile each change the expectation."""
+    shape, res, in8, out8, seed = case
+    o = kb.gemm_operands(*shape, res=res, seed=seed, exact=True, in8=in8, out8=out8)
+    v, mag = o["ref"]
+    for t in (o["x"], o["w"], o["bias"]) + (() if o["r"] is None else (o["r"],)):
+        assert torch.equal(t, t.round())
+    assert float(mag.max()) < 2 ** 24 and float(o["x"].abs().max()) <= 3 and float(o["w"].abs().max()) <= 2
+    if out8:
+        want = kb.e4m3_bytes(v * kb.f32(1.0 / o["out_scale"]))
+        assert int((want == 0x7E).sum()) > 0
+        exp = lambda t: kb.e4m3_bytes(t * kb.f32(1.0 / o["out_scale"]))  # noqa: E731
+    else:
+        assert float(torch.relu(v).max()) <= 256
+        exp = torch.relu
+    want = exp(v)
+    bm, bn = 128, 128
+    for name, wrong in kb.gemm_controls(o, bm, bn):
+        assert not torch.equal(exp(wrong), want), name
+
+
+@pytest.mark.parametrize("M,N,K,splits", [(M, N, kb.FC_K, s) for M in kb.FC_MS for N in kb.FC_NS for s in (1, 2, 4)] +
+                         [(200, 1000, 512, 2)])
+def test_fc_gemm_bar_and_controls(M, N, K, splits):
+    o = kb.fc_operands(M, K, N, seed=(600 + M + N) if K == kb.FC_K else 650)
+    v, mag = o["ref"]
+    controls = kb.fc_controls(o, splits)
+    assert len(controls) == 1 + (splits > 1) + (M > 16)
+    for out_f32 in (False, True):
+        f = (lambda t: t) if out_f32 else torch.relu
+        bnd = kb.bound(f(v), mag, K, out_bf16=not out_f32)
+        got = f(v).float().double() if out_f32 else kb.bf16r(f(v))
+        kb.assert_close(got, f(v), bnd, "rounded reference")
+        for name, wrong in controls:
+            kb.assert_rejects(got, f(wrong), bnd, name)
+
+
+def test_fc_exact_operands():
+    o = kb.fc_operands(17, kb.FC_K, 1000, seed=660, exact=True)
+    v, mag = o["ref"]
+    assert torch.equal(v, v.round()) and float(v.abs().max()) <= 256 and float(v.min()) < 0 < float(v.max())
+    for name, wrong in kb.fc_controls(o, 4):
+        assert not torch.equal(wrong, v), name
