@@ -779,6 +779,20 @@ PYBIND11_MODULE(_C, m) {
     return py::make_tuple(out, total);
   }, py::arg("arch"), py::arg("weights"), py::arg("options") = std::map<std::string, bool>{},
      py::arg("num_classes") = 1000, py::arg("image_size") = 224);
+  // ... and digests of what it packed: arena bytes, FNV-1a of the arena, {kind: digest}, [(layer, kind, off, bytes,
+  // digest)], [(layer, FragOrder name)]
+  m.def("pack_digest", [](const std::string& arch, const py::dict& weights, const std::map<std::string, bool>& options,
+                          int num_classes, int image_size) {
+    const PackDigest d = Engine::pack_digest(arch, to_weight_map(weights), engine_options(options), num_classes,
+                                             image_size);
+    py::list regions;
+    for (size_t i = 0; i < d.regions.size(); ++i) {
+      const PackRegion& r = d.regions[i];
+      regions.append(py::make_tuple(r.layer, r.kind, r.off, r.bytes, d.region_digests[i]));
+    }
+    return py::make_tuple(d.total, d.arena, d.kinds, regions, d.orders);
+  }, py::arg("arch"), py::arg("weights"), py::arg("options") = std::map<std::string, bool>{},
+     py::arg("num_classes") = 1000, py::arg("image_size") = 224);
   // host-only launch plan of a graph-captured forward: [(kernel, first op, n_ops, detail)], and the graph's ops
   // in Engine.op_list's format
   auto plan_list = [](const std::vector<Engine::PlanLine>& lines) {

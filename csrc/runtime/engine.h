@@ -35,6 +35,19 @@ struct ActShape {
   size_t elem_bytes() const { return f32 ? 4 : fp8 ? 1 : 2; }
 };
 
+// The order of a layer's second weight copy (ConvLayer::wf_off), named for the
+// kernels that read it. Engine::frag_order decides it, once per layer; the
+// packer writes it and the planner compares it with what its kernel reads.
+enum class FragOrder {
+  None,       // no second copy
+  Stream,     // bf16 in stream_frag_index order, K = kpad: the small / stream / rows / 13x13 convs, the 5x5
+              // direct conv, bottleneck56's 3x3 and expand convs
+  Stream8,    // e4m3 in conv3x3_stream8_frag_offset order
+  StemDense,  // bf16 [cout][kStemDenseK] (stem_dense_k_index)
+  AlexStem,   // bf16 [cout][kAlexStemK] (alex_stem_k)
+};
+const char* frag_order_name(FragOrder o);
+
 struct ConvLayer {
   std::string name;  // weight prefix (e.g. "layer1.0.conv1")
   std::string bn;    // BN prefix or "" (conv bias used instead)
@@ -51,16 +64,16 @@ struct ConvLayer {
   int out_act = -1;             // activation the conv writes
   bool fp8 = false;             // e4m3 weights (input activation is e4m3)
   size_t a_off = 0;             // fp8: alpha[n] = s_in * s_w[n] (fp32 [npad])
-  size_t wf_off = 0;            // weights in stream-conv fragment order (0 = none)
-  size_t wf_bytes = 0;          // ... and the size of that region
+  FragOrder frag = FragOrder::None;  // the second copy of the weights, in a kernel's own order
+  size_t wf_off = 0;            // ... its offset (an address only: `frag` says whether and what)
   // bottleneck expand conv with its stride-1 downsample folded in (conv1x1 x2):
   // [cout][kpad + ds kpad] bf16 = [W3 | Wd] and bias b3 + bd (0 = none)
   int cat_ds = -1;              // convs_ index of that downsample
   size_t cat_off = 0, cat_b_off = 0;
 
   // Layer classes shared by the weight layout (who gets a fragment-order
-  // copy at wf_off) and the planner (which kernel may run the layer); `fp8`
-  // is set by the layout pass.
+  // copy: Engine::frag_order) and the planner (which kernel may run the
+  // layer); `fp8` is set by the layout pass.
   bool plain() const { return !fp8 && !fc && !pair && !stem_pool && in_act >= 0; }  // bf16 conv on an NHWC activation
   bool plain_3x3() const { return plain() && kh == 3 && kw == 3 && pad == 1; }      // plain bf16 3x3/p1 conv
   bool plain_ds2() const { return plain() && kh == 1 && kw == 1 && stride == 2 && pad == 0; }  // 1x1/s2 downsample
@@ -165,6 +178,18 @@ struct PackRegion {
   size_t off = 0, bytes = 0;
 };
 
+// The packed arena as numbers a test can store (Engine::pack_digest): 64-bit
+// FNV-1a digests, so "the packer writes the same bytes" is checked against a
+// recorded value (tests/test_pack_golden_cpu.py).
+struct PackDigest {
+  size_t total = 0;                        // arena bytes
+  uint64_t arena = 0;                      // the whole arena
+  std::map<std::string, uint64_t> kinds;   // per region kind: one digest chained over its regions in arena order
+  std::vector<PackRegion> regions;         // as pack_audit returns them
+  std::vector<uint64_t> region_digests;    // ... and each one's own bytes
+  std::vector<std::pair<std::string, std::string>> orders;  // (layer, frag_order_name) of every layer
+};
+
 // Split-K workspace of the implicit GEMM and fc_gemm (fp32 elements, 64 MB): a
 // constant, so a host-only engine clamps split_k like one with a device.
 constexpr size_t kSplitKWsElems = (size_t)16 << 20;
@@ -190,7 +215,7 @@ struct Step {
   // (Rows28: ds_into_conv2, Conv1x1Cat: ds_into_expand)
   int ds_op = -1;
   int pool_op = -1;      // pool op whose output the conv's epilogue writes (Stream, Direct13, Direct27)
-  bool wreg = false;     // weights from the layer's wf_off copy (Stream, Rows: register-streamed; StemPoolU8: dense K)
+  bool wreg = false;     // weights from the layer's FragOrder copy (Stream, Rows: register-streamed; StemPoolU8: dense K)
   bool store_y = true;   // false: the last op's activation is not written (Stream with the pool fused, under a graph)
   bool side = false;     // runs on the side stream (fork_ds)
   int cfg = -1;          // BigTile: tile config
@@ -247,12 +272,15 @@ class Engine {
   static std::vector<PackRegion> pack_audit(const std::string& arch, const WeightMap& weights,
                                             const EngineOptions& options, size_t* total,
                                             int num_classes = 1000, int image_size = 224);
+  // The same host-only pack, as digests of the bytes it wrote.
+  static PackDigest pack_digest(const std::string& arch, const WeightMap& weights, const EngineOptions& options,
+                                int num_classes = 1000, int image_size = 224);
   // The launches of one forward. Host integer logic only.
   std::vector<Step> plan(const PlanSpec& spec) const;
   // A step's extra fields as text, e.g. "ds=layer2.0.downsample.0 wreg".
   std::string step_detail(const Step& st) const;
   // Host-only like pack_audit (the layout pass runs first: the plan reads
-  // wf_off, cat_off, npad): plan(spec) on a device with num_cus compute units,
+  // frag, cat_off, npad): plan(spec) on a device with num_cus compute units,
   // as text. *engine_ops = the graph's ops.
   struct PlanLine {
     std::string kernel, first_op, detail;
@@ -353,6 +381,7 @@ class Engine {
   void build_graph(const WeightMap& weights, bool calibrate_on_device);
   void pack_weights(const WeightMap& w);
   void layout_weights();
+  FragOrder frag_order(const ConvLayer& L) const;  // the one decision of who gets which second weight copy
   std::vector<uint8_t> pack_host(const WeightMap& w, std::vector<PackRegion>* regions);
   void init_device();
   void mark_fp8();
@@ -370,7 +399,7 @@ class Engine {
   ConvArgs conv_geom(const Op& op, int B) const;
   void bind(ConvArgs& a, const Op& op, float* logits) const;
   bool bottleneck_conv3(const ConvLayer& L) const;  // L is a fused layer1 bottleneck's expand conv (fragment-order weights)
-  struct Planner;  // kernel choice and fusion for one batch size (engine.cpp)
+  struct Planner;  // kernel choice and fusion for one batch size (engine_plan.cpp)
 
   std::string arch_;
   int device_ = 0;
@@ -408,5 +437,11 @@ class Engine {
   std::vector<hipEvent_t> fork_evs_, join_evs_;     // per op
   std::map<GraphKey, hipGraphExec_t> graphs_;
 };
+
+// Host helpers the engine's translation units share (engine_pack.cpp).
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+uint16_t f2bf_host(float f);  // round to nearest even
+float bf2f_host(uint16_t b);
+uint8_t f2e4m3_host(float f);
 
 }  // namespace dmlc

@@ -1,4 +1,4 @@
-"""Host-only audit of the packed weight arena (csrc/runtime/engine.cpp
+"""Host-only audit of the packed weight arena (csrc/runtime/engine_pack.cpp
 pack_host), no GPU needed.
 
 Every write of the weight packer goes through a bounds-checked region of the

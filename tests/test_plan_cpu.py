@@ -1,4 +1,4 @@
-"""Host-only audit of the engine's launch plan (csrc/runtime/engine.cpp
+"""Host-only audit of the engine's launch plan (csrc/runtime/engine_plan.cpp
 Engine::plan), no GPU needed.
 
 Which kernel runs which layer is decided by host integer logic alone, so a

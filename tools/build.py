@@ -114,7 +114,8 @@ HIPCC_FILE_FLAGS = {"stem_pool.hip": ["-fno-honor-nans"]}
 
 def gpu_objects():
     srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")))
-    srcs += [os.path.join(CSRC, "runtime", "engine.cpp"), os.path.join(CSRC, "runtime", "gallery.cpp")]
+    srcs += [os.path.join(CSRC, "runtime", f)
+             for f in ("engine.cpp", "engine_pack.cpp", "engine_plan.cpp", "gallery.cpp")]
     srcs += sorted(glob.glob(os.path.join(CSRC, "comm", "*.cpp")))
     return srcs
 
