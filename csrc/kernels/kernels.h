@@ -318,9 +318,30 @@ bool conv3x3_stream_supported(int Hin, int Win, int Cin, int Cout, int stride = 
 // relu?(acc * alpha + bias) * out_inv_scale) [B, H, W, CO].
 bool conv3x3_stream8_supported(int Hin, int Win, int Cin, int Cout, int stride = 1);
 size_t conv3x3_stream8_frag_offset(int j, int t, int nf, int h, int lane, int KT);
+// The basic-block forms (ResNet18 / 34 layers 3-4, conv3x3_stream8_block.hip),
+// chosen by the operands of Stream8Block; inv = out_inv_scale:
+//  * res (stride 1, Cin == Cout, 14x14x256 / 7x7x512): e4m3 [B, H, W, CO], 8-B
+//    aligned. q = fma(acc, alpha[n] * inv, bias[n] * inv), then q = fma(f32(res),
+//    res_scale * inv, q), then y = e4m3(med3(q, relu ? 0 : -448, 448));
+//  * stride 2 on 14x14x256 -> 7x7x512 (Cout = 2 Cin; wf [CO][9 CI], KT = 9 CI /
+//    128). With wd (e4m3 [CO][CI] in the same fragment order, KT = CI / 128)
+//    the launch also computes the block's 1x1/s2 downsample from the resident
+//    input: yd = e4m3(med3(fma(acc_d, alpha_d[n] * inv_d, bias_d[n] * inv_d),
+//    -448, 448)) [B, 7, 7, CO], inv_d = out_inv_scale_d, no ReLU.
+// res and yd may not overlap x or y.
+struct Stream8Block {
+  const void* res = nullptr;
+  float res_scale = 1.f;
+  const void* wd = nullptr;
+  const float* alpha_d = nullptr;
+  const float* bias_d = nullptr;
+  void* yd = nullptr;
+  float out_inv_scale_d = 0.f;
+};
+bool conv3x3_stream8_block_supported(int Hin, int Win, int Cin, int Cout, int stride, bool res, bool ds);
 void conv3x3_stream8(const void* x, const void* wf, const float* alpha, const float* bias, void* y, const void* zero,
                      int B, int Hin, int Win, int Cin, int Cout, int stride, bool relu, float out_inv_scale,
-                     hipStream_t s);
+                     hipStream_t s, const Stream8Block* blk = nullptr);
 void conv3x3_stream8_set_variant(int v);  // test hook (0 = the defaults; 4: 7-row strips at layer2.0.conv2)
 // Stride 2 may also compute the block's 1x1/s2 downsample conv (wd [Cout,
 // Cin], bias bd, no ReLU) from the same resident input into yd.

@@ -77,9 +77,12 @@ void Engine::build_graph(const WeightMap& weights, bool calibrate_on_device) {
     build_resnet({3, 4, 6, 3}, false);
   else if (arch_ == "resnet50")
     build_resnet({3, 4, 6, 3}, true);
-  else if (arch_ == "resnet50_fp8") {
+  else if (arch_ == "resnet50_fp8" || arch_ == "resnet18_fp8" || arch_ == "resnet34_fp8") {
     fp8_ = true;
-    build_resnet({3, 4, 6, 3}, true);
+    if (arch_ == "resnet18_fp8")
+      build_resnet({2, 2, 2, 2}, false);
+    else
+      build_resnet({3, 4, 6, 3}, arch_ == "resnet50_fp8");
     mark_fp8();
     if (calibrate_on_device) {
       calibrate(weights);
@@ -322,7 +325,28 @@ void Engine::build_alexnet() {
 // e4m3 for the fp8 implicit GEMM: slower, off.) The stem and layer1's
 // 64-channel inner convs stay bf16 (Cin = 64 is below the fp8 kernels'
 // 128-channel K-tile).
+//
+// Basic-block graphs (resnet18_fp8 / resnet34_fp8: no 1x1 stride-1 conv):
+// every conv output of at most 14x14 with a multiple of 128 channels is e4m3
+// with a per-tensor scale. That is layer3 and layer4 (the t1 tensors, the
+// block outputs, the two downsample outputs), whose 3x3 convs run on
+// conv3x3_stream8's basic-block forms; the stem and layers 1-2 stay bf16.
+// layer3.0's conv1 and downsample read bf16 and write e4m3.
 void Engine::mark_fp8() {
+  bool bottlenecks = false;
+  for (const ConvLayer& L : convs_) bottlenecks |= !L.fc && L.kh == 1 && L.stride == 1;
+  if (!bottlenecks) {
+    chan_act_.assign(shapes_.size(), false);
+    for (const Op& op : ops_) {
+      if (op.type != OpType::Conv || convs_[op.conv].fc) continue;
+      ActShape& os = shapes_[op.out];
+      if (os.H <= 14 && os.C % 128 == 0 && !os.f32) os.fp8 = true;
+    }
+    for (const Op& op : ops_)
+      if (op.type == OpType::Conv && op.res >= 0 && shapes_[op.res].fp8 != shapes_[op.out].fp8)
+        throw std::runtime_error("mark_fp8: residual and output dtypes differ at " + op.name);
+    return;
+  }
   const bool fp8_3x3 = opt_.fp8_3x3;
   std::vector<bool> near_3x3(shapes_.size(), false);  // read or written by a 3x3 conv
   for (const Op& op : ops_)
@@ -667,10 +691,23 @@ void Engine::run_ops(const std::vector<Step>& steps, const Request& req, hipStre
                    Lp->stride, Lp->relu, st.count, cs, D ? W(D->wf_off) : nullptr, D ? F(D->b_off) : nullptr,
                    D ? acts_[d->out] : nullptr);
         break;
-      case Kernel::Stream8:
+      case Kernel::Stream8: {
+        Stream8Block blk;  // a basic block's residual, or its downsample from the same launch
+        if (res) {
+          blk.res = res;
+          blk.res_scale = shapes_[op.res].scale;
+        }
+        if (D) {
+          blk.wd = W(D->wf_off);
+          blk.alpha_d = F(D->a_off);
+          blk.bias_d = F(D->b_off);
+          blk.yd = acts_[d->out];
+          blk.out_inv_scale_d = 1.f / shapes_[d->out].scale;
+        }
         conv3x3_stream8(acts_[op.in], W(Lp->wf_off), F(Lp->a_off), F(Lp->b_off), acts_[op.out], zero_, B, isp->H,
-                        isp->W, isp->C, Lp->cout, Lp->stride, Lp->relu, 1.f / shapes_[op.out].scale, cs);
+                        isp->W, isp->C, Lp->cout, Lp->stride, Lp->relu, 1.f / shapes_[op.out].scale, cs, &blk);
         break;
+      }
       case Kernel::Rows28:
         if (D)  // the block's downsample as 2 more K steps instead of the residual read
           conv3x3_rows28(acts_[op.in], W(Lp->wf_off), F(Lp->b_off), nullptr, acts_[op.out], B, Lp->relu, cs, 0.f,

@@ -252,7 +252,9 @@ class Engine {
  public:
   // arch: resnet18 | resnet34 | resnet50 | alexnet | resnet50_fp8 (layers 2-4
   // on the block-scaled e4m3 MFMA: per-channel weight scales, per-tensor
-  // activation scales calibrated at load time on a synthetic batch)
+  // activation scales calibrated at load time on a synthetic batch) |
+  // resnet18_fp8 | resnet34_fp8 (layers 3-4 in e4m3 on conv3x3_stream8's
+  // basic-block forms, the same scales; layers 1-2 and the stem stay bf16)
   Engine(const std::string& arch, const WeightMap& weights, int device, int num_classes = 1000,
          int image_size = 224, const EngineOptions& options = {});
   // A replica of `src` on `device` (same graph, packing, calibration) whose

@@ -166,8 +166,14 @@ FragOrder Engine::frag_order(const ConvLayer& L) const {
   claim(L.plain() && L.kh == 5 && L.kw == 5 && L.stride == 1 && conv5x5_27_supported(is.H, is.W, is.C, L.cout, L.pad),
         FragOrder::Stream);
   // e4m3 fragment-order copy for conv3x3_stream8.hip
+  // (its basic-block forms: the channel-doubling 3x3/s2, and the block's
+  // 1x1/s2 downsample the same launch computes, KT = Cin / 128)
   claim(L.fp8 && !L.fc && L.in_act >= 0 && L.kh == 3 && L.kw == 3 && L.pad == 1 && L.kpad == 9 * L.cin &&
-            conv3x3_stream8_supported(is.H, is.W, is.C, L.cout, L.stride),
+            (conv3x3_stream8_supported(is.H, is.W, is.C, L.cout, L.stride) ||
+             conv3x3_stream8_block_supported(is.H, is.W, is.C, L.cout, L.stride, false, false)),
+        FragOrder::Stream8);
+  claim(L.fp8 && !L.fc && L.in_act >= 0 && L.kh == 1 && L.kw == 1 && L.pad == 0 && L.stride == 2 && L.kpad == L.cin &&
+            conv3x3_stream8_block_supported(is.H, is.W, is.C, L.cout, 2, false, true),
         FragOrder::Stream8);
   claim(bottleneck_conv3(L), FragOrder::Stream);  // fragment-order copy for bottleneck56.hip's expand conv
   // dense-K order for the one-image-per-workgroup stem (stem_dense_k_index)

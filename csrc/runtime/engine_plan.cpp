@@ -161,8 +161,14 @@ struct Engine::Planner {
       return Path::Direct13;
     // e4m3 in and out (fp8_3x3_in): whole images per workgroup, once the batch
     // fills the CUs (query batches: the e4m3 implicit GEMM)
-    if (L.fp8 && !L.fc && L.kh == 3 && L.kw == 3 && L.pad == 1 && L.frag == FragOrder::Stream8 && op.res < 0 &&
-        shapes[op.out].fp8 && 4 * B >= cus && conv3x3_stream8_supported(is.H, is.W, is.C, L.cout, L.stride))
+    // (a basic block's conv2 with its e4m3 residual, and its channel-doubling
+    // stride-2 conv1: the basic-block forms)
+    if (L.fp8 && !L.fc && L.kh == 3 && L.kw == 3 && L.pad == 1 && L.frag == FragOrder::Stream8 &&
+        shapes[op.out].fp8 && 4 * B >= cus &&
+        (op.res < 0 ? conv3x3_stream8_supported(is.H, is.W, is.C, L.cout, L.stride) ||
+                          conv3x3_stream8_block_supported(is.H, is.W, is.C, L.cout, L.stride, false, false)
+                    : shapes[op.res].fp8 && shapes[op.res].cscale.empty() &&
+                          conv3x3_stream8_block_supported(is.H, is.W, is.C, L.cout, L.stride, true, false)))
       return Path::Stream8;
     if (opt.direct27 && L.plain() && L.kh == 5 && L.kw == 5 && L.stride == 1 && L.relu && L.frag == FragOrder::Stream &&
         L.kpad == 1600 && !shapes[op.out].f32 && conv5x5_27_supported(is.H, is.W, is.C, L.cout, L.pad))
@@ -213,8 +219,6 @@ struct Engine::Planner {
     if (pool.type != OpType::AvgPoolGlobal || fc.type != OpType::Conv || sm.type != OpType::SoftmaxTop1) return false;
     if (fc.in != pool.out || sm.in != fc.out || !shapes[fc.out].f32 || shapes[pool.out].fp8) return false;
     const ConvLayer& L = convs[fc.conv];
-    // (an e4m3 pool input, ResNet50 fp8: pooled from e4m3 in the head, C >= 2048)
-    if (shapes[pool.in].fp8 && shapes[pool.in].C < 2048) return false;
     return L.fc && !L.fp8 && !L.relu && L.cin == shapes[pool.in].C && head_supported(L.cin, L.cout, L.kpad, L.npad);
   }
 
@@ -242,6 +246,12 @@ struct Engine::Planner {
     const Op& c = ops[oi + 1];
     const ConvLayer& D = convs[d.conv];
     const ConvLayer& L = convs[c.conv];
+    // e4m3 in and out: conv3x3_stream8's downsample phase (layer4.0 of resnet18_fp8 / resnet34_fp8)
+    if (D.fp8)
+      return d.in == c.in && !D.fc && D.kh == 1 && D.kw == 1 && D.stride == 2 && D.pad == 0 && !D.relu && d.res < 0 &&
+             D.cout == L.cout && c.res < 0 && D.frag == FragOrder::Stream8 && path[oi + 1] == Path::Stream8 &&
+             shapes[d.out].fp8 && shapes[d.out].cscale.empty() &&
+             conv3x3_stream8_block_supported(shapes[c.in].H, shapes[c.in].W, shapes[c.in].C, L.cout, L.stride, false, true);
     return d.in == c.in && D.plain_ds2() && !D.relu && d.res < 0 && D.cout == L.cout && L.stride == 2 &&
            !shapes[d.out].fp8 && !shapes[d.out].f32 &&
            (path[oi + 1] == Path::Stream || (path[oi + 1] == Path::Small && D.frag == FragOrder::Stream));
@@ -465,6 +475,7 @@ struct Engine::Planner {
         break;
       case Path::Stream8:
         st.kernel = Kernel::Stream8;
+        st.ds_op = ds;
         break;
       case Path::Rows28:
         st.kernel = Kernel::Rows28;
@@ -599,7 +610,9 @@ struct Engine::Planner {
           if (pooled) {  // pooled by the last conv's epilogue; fc + softmax / top-1 in one launch, or as ops
             emit(Kernel::None, oi, 1);
             if (head_fusable(oi)) emit(Kernel::HeadPooled, oi + 1, 2);
-          } else if (head_fusable(oi) && B >= kPoolThenHeadB) {
+          } else if (head_fusable(oi) && (B >= kPoolThenHeadB || (shapes[op.in].fp8 && shapes[op.in].C < 2048))) {
+            // (and at every batch where head_fused cannot pool the input:
+            // e4m3 with C < 2048, resnet18_fp8 / resnet34_fp8)
             // throughput batches: pool once, then fc + softmax/top-1 on the
             // pooled rows (head_fused pools its images again in every class
             // split: resnet50_fp8 b256 86 us, 8 x 25.7 MB of e4m3 reads)

@@ -630,23 +630,48 @@ def stream8_weight_frag(w_q: torch.Tensor, cout: int) -> torch.Tensor:
 
 
 def conv3x3_stream8(x: torch.Tensor, w_q: torch.Tensor, alpha: torch.Tensor, bias: torch.Tensor, relu: bool = True,
-                    out_scale: float = 1.0, frag: torch.Tensor | None = None, stride: int = 1) -> torch.Tensor:
+                    out_scale: float = 1.0, frag: torch.Tensor | None = None, stride: int = 1, *,
+                    res: torch.Tensor | None = None, res_scale: float = 1.0, wd: torch.Tensor | None = None,
+                    alpha_d: torch.Tensor | None = None, bias_d: torch.Tensor | None = None,
+                    out_scale_d: float | None = None):
     """e4m3 3x3/p1 conv (conv3x3_stream8.hip) on e4m3 NHWC: stride 1 on
     [B,14,14,256] / [B,7,7,512], stride 2 on [B,28,28,256] / [B,14,14,512]:
     e4m3(relu?(acc * alpha + bias) / out_scale) with acc = conv of the e4m3
-    values. w_q / alpha: pack_conv_weight_fp8 (alpha = s_x * s_w)."""
-    _need_cuda(x, w_q, alpha, bias)
+    values. w_q / alpha: pack_conv_weight_fp8 (alpha = s_x * s_w).
+
+    The basic-block forms (ResNet18 / 34 layers 3-4): ``res`` (e4m3, the
+    output's shape; stride 1 on 14x14x256 / 7x7x512) adds res * res_scale
+    before the ReLU; w_q of [512, 9 * 256] at stride 2 on [B,14,14,256] is the
+    channel-doubling conv, and with ``wd`` (e4m3 [512, 256], alpha_d, bias_d,
+    out_scale_d) the same launch also returns the block's 1x1/s2 downsample
+    yd = e4m3((acc_d * alpha_d + bias_d) / out_scale_d), no ReLU: (y, yd)."""
+    _need_cuda(x, w_q, alpha, bias, res, wd, alpha_d, bias_d)
     C = native()
     B, H, W, Cin = x.shape
-    cout = Cin
-    if x.dtype != FP8 or not C.conv3x3_stream8_supported(H, W, Cin, cout, stride) or w_q.shape[1] != 9 * Cin:
+    cout = 2 * Cin if stride == 2 and w_q.shape[0] == 2 * Cin else Cin
+    block = res is not None or wd is not None or cout != Cin
+    ok = (C.conv3x3_stream8_block_supported(H, W, Cin, cout, stride, res is not None, wd is not None) if block
+          else C.conv3x3_stream8_supported(H, W, Cin, cout, stride))
+    if x.dtype != FP8 or not ok or w_q.shape[1] != 9 * Cin:
         raise ValueError("conv3x3_stream8: unsupported shape / dtype")
     wf = stream8_weight_frag(w_q, cout) if frag is None else frag
     y = torch.empty(B, H // stride, W // stride, cout, dtype=FP8, device=x.device)
+    extra, yd = {}, None
+    if res is not None:
+        if tuple(res.shape) != tuple(y.shape):
+            raise ValueError("conv3x3_stream8: res has the output's shape")
+        extra.update(res=_ptr(_e4m3(res, "conv3x3_stream8: res")), res_scale=float(res_scale))
+    if wd is not None:
+        if tuple(wd.shape) != (cout, Cin) or alpha_d is None or bias_d is None or out_scale_d is None:
+            raise ValueError("conv3x3_stream8: wd is e4m3 [Cout, Cin] with alpha_d, bias_d and out_scale_d")
+        yd = torch.empty_like(y)
+        wdf = stream8_weight_frag(_e4m3(wd, "conv3x3_stream8: wd"), cout)
+        extra.update(wd=_ptr(wdf), alpha_d=_ptr(_f32(alpha_d, cout, "alpha_d")),
+                     bias_d=_ptr(_f32(bias_d, cout, "bias_d")), yd=_ptr(yd), out_inv_scale_d=1.0 / out_scale_d)
     C.conv3x3_stream8(_ptr(x.contiguous()), _ptr(wf), _ptr(alpha.float().contiguous()), _ptr(bias.float().contiguous()),
                       _ptr(y), _ptr(_zero_page(x.device)), B, H, W, Cin, cout, stride, relu, 1.0 / out_scale,
-                      _stream())
-    return y
+                      _stream(), **extra)
+    return y if wd is None else (y, yd)
 
 
 def maxpool2d(x: torch.Tensor, k: int = 3, stride: int = 2, pad: int = 1) -> torch.Tensor:
