@@ -419,6 +419,60 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("x"), py::arg("ldx"), py::arg("w"), py::arg("ldw"), py::arg("bias"), py::arg("y"), py::arg("ldo"),
         py::arg("out_f32"), py::arg("B"), py::arg("K"), py::arg("N"), py::arg("Npad"), py::arg("relu"),
         py::arg("stream"));
+  // e4m3 fully connected layers (fc8.hip)
+  m.def("quant_e4m3", [](uintptr_t x, uintptr_t y, int B, int K, float inv_scale, uintptr_t stream) {
+    quant_e4m3(P<void>(x), P<void>(y), B, K, inv_scale, S(stream));
+  }, py::arg("x"), py::arg("y"), py::arg("B"), py::arg("K"), py::arg("inv_scale"), py::arg("stream"));
+  m.def("fc_small8_supported", &fc_small8_supported);
+  m.def("fc_small8", [](uintptr_t x, int ldx, uintptr_t w, int ldw, uintptr_t alpha, uintptr_t bias, uintptr_t y,
+                        int ldo, bool out_f32, bool out_fp8, float out_inv_scale, int B, int K, int N, int Npad,
+                        bool relu, uintptr_t stream) {
+    fc_small8(P<void>(x), ldx, P<void>(w), ldw, P<float>(alpha), P<float>(bias), P<void>(y), ldo, out_f32, out_fp8,
+              out_inv_scale, B, K, N, Npad, relu, S(stream));
+  }, py::arg("x"), py::arg("ldx"), py::arg("w"), py::arg("ldw"), py::arg("alpha"), py::arg("bias"), py::arg("y"),
+        py::arg("ldo"), py::arg("out_f32"), py::arg("out_fp8"), py::arg("out_inv_scale"), py::arg("B"), py::arg("K"),
+        py::arg("N"), py::arg("Npad"), py::arg("relu"), py::arg("stream"));
+  // a [M,1,1,K] e4m3 layer's ConvArgs for the fc_gemm8 bindings
+  auto fc8_args = [](uintptr_t x, uintptr_t w, uintptr_t alpha, uintptr_t bias, uintptr_t y, uintptr_t ws,
+                     uintptr_t zero, int M, int K, int N, int Npad, int ldo, bool relu, bool out_f32, bool out_fp8,
+                     float out_inv_scale) {
+    ConvArgs a;
+    a.x = P<void>(x);
+    a.w = P<void>(w);
+    a.alpha = P<float>(alpha);
+    a.bias = P<float>(bias);
+    a.y = P<void>(y);
+    a.ws = P<float>(ws);
+    a.zero = P<void>(zero);
+    a.B = M;
+    a.H = a.W = a.Ho = a.Wo = 1;
+    a.Cin = a.Kpad = K;
+    a.N = N;
+    a.Npad = Npad;
+    a.ldo = ldo;
+    a.relu = relu;
+    a.in_fp8 = true;
+    a.out_f32 = out_f32;
+    a.out_fp8 = out_fp8;
+    a.out_inv_scale = out_inv_scale;
+    return a;
+  };
+  m.def("fc_gemm8_supported", [=](int M, int K, int N, int Npad, int ldo, bool out_f32, bool out_fp8) {
+    return fc_gemm8_supported(fc8_args(0, 0, 0, 0, 0, 0, 0, M, K, N, Npad, ldo, false, out_f32, out_fp8, 1.f));
+  }, py::arg("M"), py::arg("K"), py::arg("N"), py::arg("Npad"), py::arg("ldo"), py::arg("out_f32") = false,
+        py::arg("out_fp8") = false);
+  m.def("fc_gemm8_splits", [=](int M, int K, int Npad, int num_cus) {
+    return fc_gemm8_splits(fc8_args(0, 0, 0, 0, 0, 0, 0, M, K, Npad, Npad, Npad, false, false, false, 1.f), num_cus);
+  });
+  // splits 0: fc_gemm8_splits for the device's CU count; ws: splits * M * Npad floats
+  m.def("fc_gemm8", [=](uintptr_t x, uintptr_t w, uintptr_t alpha, uintptr_t bias, uintptr_t y, uintptr_t ws,
+                        uintptr_t zero, int M, int K, int N, int Npad, int ldo, bool relu, bool out_f32, bool out_fp8,
+                        float out_inv_scale, int splits, uintptr_t stream) {
+    const ConvArgs a = fc8_args(x, w, alpha, bias, y, ws, zero, M, K, N, Npad, ldo, relu, out_f32, out_fp8, out_inv_scale);
+    fc_gemm8(a, splits > 0 ? splits : fc_gemm8_splits(a, device_cus()), S(stream));
+  }, py::arg("x"), py::arg("w"), py::arg("alpha"), py::arg("bias"), py::arg("y"), py::arg("ws"), py::arg("zero"),
+        py::arg("M"), py::arg("K"), py::arg("N"), py::arg("Npad"), py::arg("ldo"), py::arg("relu"), py::arg("out_f32"),
+        py::arg("out_fp8"), py::arg("out_inv_scale"), py::arg("splits"), py::arg("stream"));
   m.def("conv3x3_stream8_supported", &conv3x3_stream8_supported);
   m.def("conv3x3_stream8_frag_offset", &conv3x3_stream8_frag_offset);
   m.def("conv3x3_stream8_set_variant", &conv3x3_stream8_set_variant);

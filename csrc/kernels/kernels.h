@@ -473,6 +473,28 @@ bool fc_small_supported(int B, int K, int ldx, int ldw);
 void fc_small(const void* x, int ldx, const void* w, int ldw, const float* bias, void* y, int ldo, bool out_f32,
               int B, int K, int N, int Npad, bool relu, hipStream_t s);
 
+// e4m3 fully connected layers (fc8.hip: the alexnet_fp8 classifier). Codes are
+// OCP e4m3 bytes; y = act((sum_k cx[b][k] cw[n][k]) alpha[n] + bias[n]) as
+// bf16, fp32 (out_f32) or e4m3(y out_inv_scale), saturating (out_fp8).
+// quant_e4m3: bf16 rows x [B, K] (dense) -> y = e4m3(x inv_scale), saturating
+// at +-448; K % 8 == 0, x 16-B and y 8-B aligned.
+void quant_e4m3(const void* x, void* y, int B, int K, float inv_scale, hipStream_t s);
+// B <= 16: fc_small's weight-streaming split on the block-scaled fp8 MFMA.
+// x e4m3 [B, ldx], w e4m3 [Npad, ldw] (the packer's rows), alpha / bias fp32
+// [Npad]; K % 128 == 0, ldx / ldw multiples of 16 and >= K, x and w 16-B aligned.
+bool fc_small8_supported(int B, int K, int ldx, int ldw);
+void fc_small8(const void* x, int ldx, const void* w, int ldw, const float* alpha, const float* bias, void* y, int ldo,
+               bool out_f32, bool out_fp8, float out_inv_scale, int B, int K, int N, int Npad, bool relu,
+               hipStream_t s);
+// M = B <= 256: fc_gemm's design with K blocks of 128 e4m3 bytes. ConvArgs of
+// a [B,1,1,K] layer with in_fp8 (x [B, Kpad], w [Npad, Kpad], alpha, bias, zero,
+// ws >= splits * B * Npad floats, all 16-B aligned); Kpad % 128 == 0, Npad %
+// 128 == 0, N % 4 == 0, ldo % 4 == 0; out_f32 / out_fp8 / neither (bf16). The
+// partials are reduced by a kernel of its own (alpha, bias, ReLU, output type).
+bool fc_gemm8_supported(const ConvArgs& a);
+int fc_gemm8_splits(const ConvArgs& a, int num_cus);  // fc_gemm_splits' rule in 128-K blocks
+void fc_gemm8(const ConvArgs& a, int splits, hipStream_t s);
+
 // Row-wise softmax + top-1 over fp32 logits [B, ld] (first N columns).
 void softmax_top1(const float* logits, int B, int N, int ld, int32_t* idx, float* prob,
                   hipStream_t s);

@@ -39,6 +39,7 @@ bool EngineOptions::set(const std::string& name, bool v) {
       {"rows28", &EngineOptions::rows28},           {"stem_roles", &EngineOptions::stem_roles},
       {"stem_dense", &EngineOptions::stem_dense},
       {"fc_gemm", &EngineOptions::fc_gemm},
+      {"fc8", &EngineOptions::fc8},
       {"igemm_small_m", &EngineOptions::igemm_small_m},
       {"small_conv", &EngineOptions::small_conv},
   };
@@ -92,7 +93,13 @@ void Engine::build_graph(const WeightMap& weights, bool calibrate_on_device) {
     }
   }
   else if (arch_ == "alexnet")
-    build_alexnet();
+    build_alexnet(false);
+  else if (arch_ == "alexnet_fp8") {
+    fp8_ = true;
+    build_alexnet(true);
+    mark_fp8();
+    if (calibrate_on_device) calibrate(weights);  // (host-only audit: unit scales)
+  }
   else
     throw std::invalid_argument("unknown arch: " + arch_);
 }
@@ -207,8 +214,10 @@ int Engine::fc(int in, const std::string& name, int cout, bool relu, bool last) 
   }
   L.cout = cout;
   L.relu = relu;
+  L.in_act = in;
   convs_.push_back(L);
   const int out = add_act(ActShape{1, 1, cout, last});
+  convs_.back().out_act = out;
   ops_.push_back(Op{OpType::Conv, in, out, -1, (int)convs_.size() - 1, 0, 0, 0, name});
   return out;
 }
@@ -278,7 +287,7 @@ void Engine::build_resnet(const std::vector<int>& blocks, bool bottleneck) {
   ops_.push_back(Op{OpType::SoftmaxTop1, logits_act_, -1, -1, -1, 0, 0, 0, "softmax_top1"});
 }
 
-void Engine::build_alexnet() {
+void Engine::build_alexnet(bool fp8) {
   const int S = image_size_;
   stem_pad_ = 2;  // packed RGB image with the 11x11/s4 stem's padding built in
   int x = add_act(ActShape{S + 4, stem_row_width(S, 2, 11, 4), 3, false});
@@ -308,6 +317,11 @@ void Engine::build_alexnet() {
       x = y;
     }
   }
+  if (fp8) {  // the classifier's input as e4m3 (mark_fp8 sets the dtypes): one more activation than `alexnet`
+    const int q = add_act(shapes_[x]);
+    ops_.push_back(Op{OpType::QuantE4m3, x, q, -1, -1, 0, 0, 0, "classifier.quant"});
+    x = q;
+  }
   x = fc(x, "classifier.1", 4096, true, false);
   x = fc(x, "classifier.4", 4096, true, false);
   logits_act_ = fc(x, "classifier.6", num_classes_, false, true);
@@ -332,7 +346,22 @@ void Engine::build_alexnet() {
 // block outputs, the two downsample outputs), whose 3x3 convs run on
 // conv3x3_stream8's basic-block forms; the stem and layers 1-2 stay bf16.
 // layer3.0's conv1 and downsample read bf16 and write e4m3.
+//
+// AlexNet (alexnet_fp8): only the classifier, where the weight bytes are. The
+// quantise op's output and classifier.1's output are e4m3 with per-tensor
+// scales, so classifier.1 and classifier.4 read e4m3 (fc8.hip); classifier.4
+// writes bf16 (the vector embed() returns and classifier.6 reads).
 void Engine::mark_fp8() {
+  for (size_t i = 0; i < ops_.size(); ++i) {
+    if (ops_[i].type != OpType::QuantE4m3) continue;
+    chan_act_.assign(shapes_.size(), false);
+    shapes_[ops_[i].out].fp8 = true;
+    if (i + 1 >= ops_.size() || ops_[i + 1].type != OpType::Conv || !convs_[ops_[i + 1].conv].fc ||
+        ops_[i + 1].in != ops_[i].out)
+      throw std::runtime_error("mark_fp8: the quantise op must feed an fc layer");
+    shapes_[ops_[i + 1].out].fp8 = true;
+    return;
+  }
   bool bottlenecks = false;
   for (const ConvLayer& L : convs_) bottlenecks |= !L.fc && L.kh == 1 && L.stride == 1;
   if (!bottlenecks) {
@@ -427,7 +456,15 @@ void Engine::calibrate(const WeightMap& w) {
   ro.ds_into_expand = false;
   ro.fused_bottleneck = false;
   Engine ref(arch_.substr(0, arch_.find("_fp8")), w, device_, num_classes_, image_size_, ro);
-  if (ref.num_activations() != num_activations()) throw std::runtime_error("calibrate: graph mismatch");
+  // activations pair by index, except a quantise op's output, which the bf16
+  // graph does not have: it takes the tensor it is quantised from
+  std::vector<int> ref_of(num_activations(), -1);
+  std::vector<int> quant_src(num_activations(), -1);
+  for (const Op& op : ops_)
+    if (op.type == OpType::QuantE4m3) quant_src[op.out] = op.in;
+  int nref = 0;
+  for (int i = 0; i < num_activations(); ++i) ref_of[i] = quant_src[i] >= 0 ? ref_of[quant_src[i]] : nref++;
+  if (ref.num_activations() != nref) throw std::runtime_error("calibrate: graph mismatch");
   ref.reserve(Bc);
   const size_t img_bytes = (size_t)Bc * image_size_ * image_size_ * 3;
   std::vector<uint8_t> host(img_bytes);
@@ -448,7 +485,7 @@ void Engine::calibrate(const WeightMap& w) {
     if (!shapes_[i].fp8) continue;
     const size_t n = shapes_[i].elems_per_image() * Bc;
     std::vector<uint16_t> a(n);
-    DMLC_HIP_CHECK(hipMemcpy(a.data(), ref.activation(i), n * 2, hipMemcpyDeviceToHost));
+    DMLC_HIP_CHECK(hipMemcpy(a.data(), ref.activation(ref_of[i]), n * 2, hipMemcpyDeviceToHost));
     float amax = 0.f;
     for (uint16_t v : a) amax = std::max(amax, std::fabs(bf2f_host(v)));
     shapes_[i].scale = std::max(amax, 1e-6f) / 448.f;
@@ -620,6 +657,23 @@ void Engine::run_ops(const std::vector<Step>& steps, const Request& req, hipStre
         const ActShape& os = shapes_[op.out];
         fc_small(acts_[op.in], L.cin, W(L.w_off), L.kpad, F(L.b_off), (os.f32 && logits) ? (void*)logits : acts_[op.out],
                  L.cout, os.f32, B, L.cin, L.cout, L.npad, L.relu, cs);
+        break;
+      }
+      case Kernel::QuantE4m3:
+        quant_e4m3(acts_[op.in], acts_[op.out], B, (int)isp->elems_per_image(), 1.f / shapes_[op.out].scale, s);
+        break;
+      case Kernel::FcSmall8: {
+        const ConvLayer& L = *Lp;
+        const ActShape& os = shapes_[op.out];
+        fc_small8(acts_[op.in], L.cin, W(L.w_off), L.kpad, F(L.a_off), F(L.b_off),
+                  (os.f32 && logits) ? (void*)logits : acts_[op.out], L.cout, os.f32, os.fp8,
+                  os.fp8 ? 1.f / os.scale : 1.f, B, L.cin, L.cout, L.npad, L.relu, cs);
+        break;
+      }
+      case Kernel::FcGemm8: {
+        ConvArgs a = conv_geom(op, B);
+        bind(a, op, logits);
+        fc_gemm8(a, st.count, cs);
         break;
       }
       case Kernel::Conv1x1Cat: {

@@ -20,7 +20,10 @@
 
 namespace dmlc {
 
-enum class OpType { Preprocess, Conv, StemPool, MaxPool, AvgPoolGlobal, AvgPoolAdaptive, SoftmaxTop1 };
+enum class OpType {
+  Preprocess, Conv, StemPool, MaxPool, AvgPoolGlobal, AvgPoolAdaptive, SoftmaxTop1,
+  QuantE4m3  // bf16 activation -> e4m3 with the output's per-tensor scale (alexnet_fp8's classifier input)
+};
 
 struct ActShape {
   int H = 0, W = 0, C = 0;
@@ -143,6 +146,9 @@ struct EngineOptions {
   bool direct13 = true;          // AlexNet's 13x13 3x3 convs with the image resident in LDS (conv_direct.hip)
   bool direct27 = true;          // AlexNet's 5x5 conv on 27x27x64 the same way (conv_direct.hip)
   bool fc_small = true;          // weight-streaming GEMV for fc layers at B <= 16 (fc_small.hip)
+  // e4m3 fc layers (alexnet_fp8's classifier.1 / .4) on fc8.hip: fc_small8 at B <= 16, fc_gemm8 at B <= 256
+  // (off, and above 256: the e4m3 implicit GEMM)
+  bool fc8 = true;
   // downsample convs on a side stream: measured slower (the branch slows its
   // sibling conv1 by 10-12 us and adds ~10 us of fork/join gaps per block:
   // profiles/r1_fork_ds_timeline.txt); kept to test the side-stream path
@@ -203,7 +209,7 @@ enum class Kernel {
   AlexStem, StemPoolU8, StemPool, FcSmall, Conv1x1Cat, Conv1x1Chain, Bottleneck56, Bottleneck56Head, Block,
   S2Rows, S2Rows128, Stream, Stream8, Rows28, Rows, Small, Direct13, Direct27, Conv1x1, BigTile, Igemm, FcGemm,
   HeadPooled, HeadFused, AvgPoolGlobal, AvgPoolAdaptive, MaxPool, Preprocess, PackTensor, SoftmaxTop1, SoftmaxTopK,
-  Embed
+  Embed, QuantE4m3, FcSmall8, FcGemm8
 };
 const char* kernel_name(Kernel k);
 
@@ -219,7 +225,7 @@ struct Step {
   bool store_y = true;   // false: the last op's activation is not written (Stream with the pool fused, under a graph)
   bool side = false;     // runs on the side stream (fork_ds)
   int cfg = -1;          // BigTile: tile config
-  // Rows / StemPool / StemPoolU8: strip; Small: mf; BigTile / FcGemm: K splits; SoftmaxTopK: k;
+  // Rows / StemPool / StemPoolU8: strip; Small: mf; BigTile / FcGemm / FcGemm8: K splits; SoftmaxTopK: k;
   // Embed: the pixels it averages (0: src_op's output is the feature row itself)
   int count = 0;
   int src_op = -1;       // Embed: the op whose output activation it reads
@@ -254,7 +260,9 @@ class Engine {
   // on the block-scaled e4m3 MFMA: per-channel weight scales, per-tensor
   // activation scales calibrated at load time on a synthetic batch) |
   // resnet18_fp8 | resnet34_fp8 (layers 3-4 in e4m3 on conv3x3_stream8's
-  // basic-block forms, the same scales; layers 1-2 and the stem stay bf16)
+  // basic-block forms, the same scales; layers 1-2 and the stem stay bf16) |
+  // alexnet_fp8 (classifier.1 / classifier.4 read e4m3 on fc8.hip; the feature
+  // convs, classifier.4's output and classifier.6 stay bf16)
   Engine(const std::string& arch, const WeightMap& weights, int device, int num_classes = 1000,
          int image_size = 224, const EngineOptions& options = {});
   // A replica of `src` on `device` (same graph, packing, calibration) whose
@@ -376,7 +384,7 @@ class Engine {
            int pad, bool relu, int res = -1);
   int fc(int in, const std::string& name, int cout, bool relu, bool last);
   void build_resnet(const std::vector<int>& blocks, bool bottleneck);
-  void build_alexnet();
+  void build_alexnet(bool fp8);
   struct HostOnly {};
   Engine(HostOnly, const std::string& arch, const WeightMap& weights, int num_classes, int image_size,
          const EngineOptions& options);
@@ -411,7 +419,7 @@ class Engine {
   int max_batch_ = 0;
   int stem_pad_ = 0;
   EngineOptions opt_;
-  bool fp8_ = false;  // resnet50_fp8
+  bool fp8_ = false;  // an e4m3 arch (*_fp8)
 
   std::vector<ActShape> shapes_;
   std::vector<bool> chan_act_;  // activations with per-channel e4m3 scales (mark_fp8 -> calibrate)

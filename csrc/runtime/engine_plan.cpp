@@ -81,8 +81,9 @@ const char* kernel_name(Kernel k) {
       "None", "AlexStem", "StemPoolU8", "StemPool", "FcSmall", "Conv1x1Cat", "Conv1x1Chain", "Bottleneck56",
       "Bottleneck56Head", "Block", "S2Rows", "S2Rows128", "Stream", "Stream8", "Rows28", "Rows", "Small", "Direct13",
       "Direct27", "Conv1x1", "BigTile", "Igemm", "FcGemm", "HeadPooled", "HeadFused", "AvgPoolGlobal",
-      "AvgPoolAdaptive", "MaxPool", "Preprocess", "PackTensor", "SoftmaxTop1", "SoftmaxTopK", "Embed"};
-  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::Embed + 1, "one name per Kernel");
+      "AvgPoolAdaptive", "MaxPool", "Preprocess", "PackTensor", "SoftmaxTop1", "SoftmaxTopK", "Embed", "QuantE4m3",
+      "FcSmall8", "FcGemm8"};
+  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::FcGemm8 + 1, "one name per Kernel");
   return names[(size_t)k];
 }
 
@@ -405,6 +406,18 @@ struct Engine::Planner {
     // block's conv1 (both read the block input; conv2 joins them through the
     // residual). The fused multi-op kernels stay on the main stream.
     const bool side = side_ready && op.side;
+    // e4m3 fc layers (alexnet_fp8): the weight stream at query batches, the LDS-ring GEMM up to 256 rows;
+    // otherwise the e4m3 implicit GEMM below, which takes a [B,1,1,K] layer as it stands
+    if (L.fc && L.fp8 && opt.fc8 && !side) {
+      if (fc_small8_supported(B, L.cin, L.cin, L.kpad)) return (void)emit(Kernel::FcSmall8, oi, 1);
+      const ConvArgs a = e.conv_geom(op, B);
+      if (fc_gemm8_supported(a) && (size_t)B * a.Npad <= kSplitKWsElems) {
+        Step& st = emit(Kernel::FcGemm8, oi, 1);
+        st.count = fc_gemm8_splits(a, cus);
+        while (st.count > 1 && ((size_t)st.count * B * a.Npad > kSplitKWsElems || (a.Kpad / 128) % st.count)) --st.count;
+        return;
+      }
+    }
     // query-sized batches: weight-streaming GEMV (AlexNet classifier)
     if (L.fc && !L.fp8 && !shapes[op.out].fp8 && opt.fc_small && fc_small_supported(B, L.cin, L.cin, L.kpad)) {
       emit(Kernel::FcSmall, oi, 1).side = side;
@@ -630,6 +643,9 @@ struct Engine::Planner {
         case OpType::SoftmaxTop1:
           emit(Kernel::SoftmaxTop1, oi, 1);
           break;
+        case OpType::QuantE4m3:
+          emit(Kernel::QuantE4m3, oi, 1);
+          break;
       }
     }
     // top-k: the plan above unchanged (its tail still writes the logits and a
@@ -680,7 +696,7 @@ std::string Engine::step_detail(const Step& st) const {
   if (st.side) add("side");
   if (st.cfg >= 0) add("cfg=" + std::to_string(st.cfg));
   if (st.count > 0) {
-    const char* what = st.kernel == Kernel::Small ? "mf=" : st.kernel == Kernel::SoftmaxTopK ? "k=" : st.kernel == Kernel::Embed ? "hw=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm) ? "splits=" : "strip=";
+    const char* what = st.kernel == Kernel::Small ? "mf=" : st.kernel == Kernel::SoftmaxTopK ? "k=" : st.kernel == Kernel::Embed ? "hw=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm || st.kernel == Kernel::FcGemm8) ? "splits=" : "strip=";
     add(what + std::to_string(st.count));
   }
   return d;

@@ -977,6 +977,83 @@ def fc_small(x: torch.Tensor, w_packed: torch.Tensor, n: int, bias: torch.Tensor
     return out[:B, :n]
 
 
+def quant_e4m3(x: torch.Tensor, scale: float) -> torch.Tensor:
+    """bf16 rows [B, K] (contiguous, K % 8 == 0) -> float8_e4m3fn [B, K]:
+    e4m3(x * fp32(1 / scale)), saturating at +-448 (fc8.hip)."""
+    _need_cuda(x)
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or not x.is_contiguous() or x.shape[1] % 8 or not scale > 0:
+        raise ValueError("quant_e4m3 expects contiguous bf16 x [B, K], K % 8 == 0, and scale > 0")
+    y = torch.empty(x.shape, dtype=FP8, device=x.device)
+    native().quant_e4m3(_ptr(x), _ptr(y), x.shape[0], x.shape[1], 1.0 / scale, _stream())
+    return y
+
+
+def _fc8_operands(what, x8, w8, n, alpha, bias, out_scale, out_f32):
+    _need_cuda(x8, w8, alpha, bias)
+    x8, w8 = _e4m3(x8, what + ": x8"), _e4m3(w8, what + ": w8")
+    if x8.dim() != 2 or w8.dim() != 2 or x8.shape[1] != w8.shape[1]:
+        raise ValueError(f"{what} expects e4m3 x8 [B, K] and w8 [Npad, K]")
+    if out_f32 and out_scale is not None:
+        raise ValueError(f"{what}: the output is fp32 or e4m3 (out_scale), not both")
+    if n < 1 or n > w8.shape[0]:
+        raise ValueError(f"{what}: n outside 1..Npad")
+    dt = torch.float32 if out_f32 else FP8 if out_scale is not None else torch.bfloat16
+    npad = w8.shape[0]  # alpha / bias hold n values at least; the kernels read whole rows of Npad
+    al, bi = (torch.nn.functional.pad(_f32(t, n, f"{what}: {nm}"), (0, max(0, npad - t.numel())))
+              for t, nm in ((alpha, "alpha"), (bias, "bias")))
+    return x8, w8, al, bi, dt
+
+
+def fc_small8(x8: torch.Tensor, w8: torch.Tensor, n: int, alpha: torch.Tensor, bias: torch.Tensor,
+              relu: bool = False, out_scale: float | None = None, out_f32: bool = False,
+              out: torch.Tensor | None = None) -> torch.Tensor:
+    """e4m3 fully connected layer at B <= 16 rows (fc8.hip): act((x8 . w8[n])
+    alpha[n] + bias[n]). x8 e4m3 codes [B, K], w8 e4m3 [Npad, K]
+    (``pack_conv_weight_fp8``), K % 128 == 0; alpha = s_x * s_w, bias: fp32
+    [Npad]. Returns [B, n] bf16, fp32 (out_f32) or e4m3 of y / out_scale
+    (saturating), written into ``out[:B, :n]`` if given (as for ``fc_small``;
+    e4m3 also as uint8 bytes)."""
+    x8, w8, al, bi, dt = _fc8_operands("fc_small8", x8, w8, n, alpha, bias, out_scale, out_f32)
+    C = native()
+    B, K = x8.shape
+    if not C.fc_small8_supported(B, K, K, K) or w8.shape[0] < (n + 15) // 16 * 16:
+        raise ValueError("fc_small8: unsupported shape")
+    if out is None:
+        out = torch.empty(B, n, device=x8.device, dtype=dt)
+    elif out.dim() != 2 or not (out.dtype == dt or (dt == FP8 and out.dtype == torch.uint8)) or out.shape[0] < B \
+            or out.shape[1] < n or out.stride(1) != 1 or out.stride(0) < n or not out.is_cuda:
+        raise ValueError("fc_small8: out must be a [>= B, >= n] tensor of the output type with unit column stride")
+    C.fc_small8(_ptr(x8), K, _ptr(w8), K, _ptr(al), _ptr(bi), _ptr(out), out.stride(0), out_f32, dt == FP8,
+                1.0 / out_scale if dt == FP8 else 1.0, B, K, n, w8.shape[0], relu, _stream())
+    return out[:B, :n]
+
+
+def fc_gemm8(x8: torch.Tensor, w8: torch.Tensor, n: int, alpha: torch.Tensor, bias: torch.Tensor,
+             relu: bool = False, out_scale: float | None = None, out_f32: bool = False,
+             out: torch.Tensor | None = None, splits: int = 0) -> torch.Tensor:
+    """The same layer at M <= 256 rows on fc8.hip's LDS-ring GEMM: w8 [Npad,
+    K] with Npad % 128 == 0, n % 4 == 0. splits: K slices of whole 128-K
+    blocks (0: the engine's choice). ``out``: a contiguous [>= M, n] tensor of
+    the output type; its first M rows are written and returned."""
+    x8, w8, al, bi, dt = _fc8_operands("fc_gemm8", x8, w8, n, alpha, bias, out_scale, out_f32)
+    C = native()
+    M, K = x8.shape
+    npad = w8.shape[0]
+    if not C.fc_gemm8_supported(M, K, n, npad, n, out_f32, dt == FP8):
+        raise ValueError("fc_gemm8: unsupported shape")
+    if splits <= 0:
+        splits = C.fc_gemm8_splits(M, K, npad, torch.cuda.get_device_properties(x8.device).multi_processor_count)
+    if (K // 128) % splits:
+        raise ValueError("fc_gemm8: splits must divide K / 128")
+    if out is not None and out.dim() == 2 and out.shape[0] > M:
+        out = _out_tensor(out, (out.shape[0], n), dt, x8.device, "fc_gemm8")[:M]
+    y = _out_tensor(out, (M, n), dt, x8.device, "fc_gemm8")
+    ws = torch.empty(splits * M * npad, device=x8.device, dtype=torch.float32)
+    C.fc_gemm8(_ptr(x8), _ptr(w8), _ptr(al), _ptr(bi), _ptr(y), _ptr(ws), _ptr(_zero_page(x8.device)), M, K, n, npad,
+               n, relu, out_f32, dt == FP8, 1.0 / out_scale if dt == FP8 else 1.0, splits, _stream())
+    return y
+
+
 _HEAD_WS: dict = {}
 
 

@@ -117,6 +117,7 @@ HIPCC_FILE_FLAGS = {
     # are pinned bit for bit by the suite). Not a spill fix: WIDE+DS / RES 14x14 / RES 7x7 take
     # 215 / 189 / 250 VGPRs without packed ops, 224 / 183 / 250 with them, no scratch either way.
     "conv3x3_stream8_block.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "fc8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 
