@@ -286,9 +286,13 @@ PYBIND11_MODULE(_C, m) {
     maxpool2d(P<void>(x), P<void>(y), B, H, W, C, conv_out_dim(H, k, stride, pad),
               conv_out_dim(W, k, stride, pad), k, stride, pad, S(stream));
   });
-  m.def("avgpool_global", [](uintptr_t x, uintptr_t y, int B, int HW, int C, uintptr_t stream) {
-    avgpool_global(P<void>(x), P<void>(y), B, HW, C, S(stream));
-  });
+  m.def(
+      "avgpool_global",
+      [](uintptr_t x, uintptr_t y, int B, int HW, int C, uintptr_t stream, bool in_fp8, float scale) {
+        avgpool_global(P<void>(x), P<void>(y), B, HW, C, S(stream), in_fp8, scale);
+      },
+      py::arg("x"), py::arg("y"), py::arg("B"), py::arg("HW"), py::arg("C"), py::arg("stream"),
+      py::arg("in_fp8") = false, py::arg("scale") = 1.0f);
   m.def("avgpool_adaptive", [](uintptr_t x, uintptr_t y, int B, int H, int W, int C, int Ho, int Wo,
                                uintptr_t stream) {
     avgpool_adaptive(P<void>(x), P<void>(y), B, H, W, C, Ho, Wo, S(stream));

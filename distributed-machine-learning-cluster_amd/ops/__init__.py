@@ -684,11 +684,20 @@ def maxpool2d(x: torch.Tensor, k: int = 3, stride: int = 2, pad: int = 1) -> tor
     return y
 
 
-def avgpool_global(x: torch.Tensor) -> torch.Tensor:
+def avgpool_global(x: torch.Tensor, scale: float | None = None) -> torch.Tensor:
+    """Global average of bf16, or e4m3 (value = e4m3 * ``scale``), NHWC ``x`` as bf16 [B,C]."""
     _need_cuda(x)
+    fp8 = x.dtype == FP8
+    if not fp8 and x.dtype != torch.bfloat16:
+        raise ValueError(f"avgpool_global expects bf16 or e4m3, got {x.dtype}")
+    if fp8 and scale is None:
+        raise ValueError("avgpool_global: an e4m3 input needs its scale")
+    if not fp8 and scale is not None:
+        raise ValueError("avgpool_global: scale goes with an e4m3 input")
     B, H, W, Ch = x.shape
     y = torch.empty(B, Ch, device=x.device, dtype=torch.bfloat16)
-    native().avgpool_global(_ptr(x.contiguous()), _ptr(y), B, H * W, Ch, _stream())
+    native().avgpool_global(_ptr(x.contiguous()), _ptr(y), B, H * W, Ch, _stream(), in_fp8=fp8,
+                            scale=float(scale) if fp8 else 1.0)
     return y
 
 

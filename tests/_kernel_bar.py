@@ -1,6 +1,7 @@
 """The element-wise bar of the op tests (test_kernels_fused_gpu.py,
 test_kernels_resnet_gpu.py, test_kernels_resnet50_gpu.py,
-test_kernels_gemm_gpu.py, test_kernel_bar_cpu.py): a kernel's output against
+test_kernels_gemm_gpu.py, test_kernels_stream8_block_gpu.py,
+test_kernels_stream8_gpu.py, test_kernel_bar_cpu.py): a kernel's output against
 the float64 result on the same bf16-rounded operands.
 
 A rounding argument, not a measurement. A bf16-output conv or fc with K
@@ -67,6 +68,10 @@ test_kernels_resnet50_gpu.py. The general matrix family
 split-K, 0.77 persistent, 0.97 the stem, 0.91 / 0.94 / 0.59 the e4m3 in / out,
 bf16 in / e4m3 out and e4m3 in / bf16 out forms; conv_bigtile 0.82 with slabs,
 0.81 persistent; fc_gemm 0.90; every fp32 output below 0.01.
+conv3x3_stream8's ResNet50 forms (test_kernels_stream8_gpu.py): 0.93 over the
+six shapes and the 7-row-strip variant, the figure of the float64 reference
+rounded to e4m3 against itself; avgpool_adaptive under this file's rounding
+argument for an n-term fp32 sum (test_kernels_pool_gpu.py): 0.996.
 
 Next to the bar every test keeps the project's relative-L2 bar for bf16
 outputs (5e-3), and a negative control: a reference with one realistic kernel
@@ -266,13 +271,17 @@ def fault_border_taps(ref, x, w, pad, at=0):
     return out
 
 
-def fault_border_taps_s2(ref, x, w, at=0):
+def fault_border_taps_s2(ref, x, w, at=0, kh=1):
     """The same for a 3x3/s2/p1 conv: the output row whose kh = 1 taps lie on
     the even image row `at` loses them (at = 0: output row 0, whose kh = 0
-    taps are the top padding)."""
-    lost = F.conv2d(x.double()[:, :, at:at + 1, :], w.double()[:, :, 1:2, :], None, (1, 2), (0, 1))
+    taps are the top padding). kh = 0: the output row r whose kh = 0 taps lie
+    on the odd image row `at` = 2 r - 1 (the halo row above a strip that
+    starts at output row r) loses those."""
+    assert (at + 1 - kh) % 2 == 0, (at, kh)
+    r = (at + 1 - kh) // 2
+    lost = F.conv2d(x.double()[:, :, at:at + 1, :], w.double()[:, :, kh:kh + 1, :], None, (1, 2), (0, 1))
     out = ref.clone()
-    out[:, :, at // 2:at // 2 + 1, :] -= lost
+    out[:, :, r:r + 1, :] -= lost
     return out
 
 
@@ -537,6 +546,13 @@ def e4m3_bytes(v):
     v must be exact in fp32."""
     import _e4m3_ref
     return _e4m3_ref.round_bytes(v.clamp(0, E4M3_MAX))
+
+
+def e4m3_bytes_signed(v):
+    """The same without the ReLU (a kernel's relu = False): v saturated at
+    -448 and 448 and rounded to e4m3, as bytes."""
+    import _e4m3_ref
+    return _e4m3_ref.round_bytes(v.clamp(-E4M3_MAX, E4M3_MAX))
 
 
 def fault_ds_missing(ref, x56, wd, b=0, frag=3):
@@ -1019,4 +1035,84 @@ def fc_controls(o, splits):
         s = R.clone()
         s[16:min(32, M)] = R[:min(32, M) - 16]
         out.append(("row group shift", s))
+    return out
+
+
+# ---------------------------------------------------------------- conv3x3_stream8's ResNet50 forms
+# (tests/test_kernels_stream8_gpu.py; test_kernel_bar_cpu.py checks the bar and the controls without a GPU)
+# name: (input H = W, C, stride, launcher variant, the output row at which a second workgroup's strip starts, or
+# None where a workgroup holds whole images). The two 56x56x128/s2 variants share their operands.
+STREAM8_FORMS = {
+    "28x28x128": (28, 128, 1, 0, 14),
+    "14x14x256": (14, 256, 1, 0, None),
+    "7x7x512": (7, 512, 1, 0, None),
+    "56x56x128s2": (56, 128, 2, 0, 4),
+    "56x56x128s2v4": (56, 128, 2, 4, 7),
+    "28x28x256s2": (28, 256, 2, 0, 7),
+    "14x14x512s2": (14, 512, 2, 0, None),
+}
+STREAM8_SAT_SCALE = 2.0 ** -6  # the exact operands' saturating output scale
+_STREAM8_OPERANDS = {}
+
+
+def stream8_operands(form, B, exact=False):
+    """conv3x3_stream8's operands for a form of STREAM8_FORMS, NCHW float64
+    (made once per (shape, B, exact) and shared: do not modify): e4m3 codes
+    x >= 0 and w, alpha = s_x s_w rounded to fp32, an fp32 bias, "weff" = w
+    alpha, "ref" = (ref64 before the ReLU, mag) and an output scale that puts
+    the largest relu(ref) at 400 of 448 (no power of two).
+
+    exact: codes 0..2, sparse weights in -2..2, alpha in {1/2, 1, 2}, integer
+    biases in -8..8 and out_scale = 2: every fp32 value inside the kernel is
+    exact in any order."""
+    H, C, S, _, _ = STREAM8_FORMS[form]
+    key = (H, C, S, B, exact)
+    if key in _STREAM8_OPERANDS:
+        return _STREAM8_OPERANDS[key]
+    g = torch.Generator().manual_seed(7000 + 1000 * S + 10 * H + B + 5 * exact)
+    o = {"S": S, "K": 9 * C}
+    if exact:
+        o["x"] = torch.randint(0, 3, (B, C, H, H), generator=g).double()
+        o["w"] = torch.randint(-2, 3, (C, C, 3, 3), generator=g).double() * (torch.rand(C, C, 3, 3, generator=g) < 0.005)
+        o["alpha"] = (2.0 ** torch.randint(-1, 2, (C,), generator=g)).double()
+        o["bias"] = torch.randint(-8, 9, (C,), generator=g).double()
+    else:
+        xv = torch.rand(B, C, H, H, generator=g) * 4
+        sx = f32(float(xv.max()) / E4M3_MAX)
+        o["x"] = (xv / sx).clamp(0, E4M3_MAX).to(torch.float8_e4m3fn).double()
+        o["w"], sw = e4m3_weights(torch.randn(C, C, 3, 3, generator=g) / (9 * C) ** 0.5)
+        o["alpha"] = (sx * sw).float().double()
+        o["bias"] = (torch.randn(C, generator=g) * 0.1).float().double()
+    o["weff"] = o["w"] * o["alpha"].view(-1, 1, 1, 1)
+    o["ref"] = conv_ref(o["x"], o["weff"], o["bias"], S, 1)
+    o["out_scale"] = 2.0 if exact else float(torch.relu(o["ref"][0]).max()) / 400.0
+    _STREAM8_OPERANDS[key] = o
+    return o
+
+
+def stream8_bar(o, v=None):
+    """(the expected output in its own units, its bar) of a reference v
+    (before the ReLU; default: the operands' own)."""
+    ref, mag = o["ref"]
+    inv = f32(1.0 / o["out_scale"])
+    return torch.relu(ref if v is None else v) * inv, e4m3_bound(torch.relu(ref), mag, o["K"], inv)
+
+
+def stream8_controls(form, o):
+    """Faulty references (before the ReLU) of a ResNet50 form: the kh = 0 taps
+    of the first output row of the second workgroup's strip (its halo row: the
+    image row above the strip), or of the image's top border where a workgroup
+    holds whole images; a 16-byte chunk swap in the last image; a batch shift."""
+    _, _, S, _, seam = STREAM8_FORMS[form]
+    ref = o["ref"][0]
+    if S == 1:
+        taps = fault_border_taps(ref, o["x"], o["weff"], 1, at=0 if seam is None else seam - 1)
+    elif seam is None:
+        taps = fault_border_taps_s2(ref, o["x"], o["weff"])
+    else:
+        taps = fault_border_taps_s2(ref, o["x"], o["weff"], at=2 * seam - 1, kh=0)
+    out = [("border taps" if seam is None else "seam taps", taps),
+           ("chunk swap", fault_chunk_swap(ref, b=ref.shape[0] - 1, width=16))]
+    if ref.shape[0] > 1:
+        out.append(("batch shift", fault_batch_shift(ref)))
     return out

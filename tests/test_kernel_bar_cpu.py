@@ -475,3 +475,69 @@ def test_fc_exact_operands():
     assert torch.equal(v, v.round()) and float(v.abs().max()) <= 256 and float(v.min()) < 0 < float(v.max())
     for name, wrong in kb.fc_controls(o, 4):
         assert not torch.equal(wrong, v), name
+
+
+# ---------------------------------------------------------------- conv3x3_stream8's ResNet50 forms (test_kernels_stream8_gpu.py)
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("form", list(kb.STREAM8_FORMS))
+def test_stream8_bar_and_controls(form, B):
+    """The GPU test's own operands: the float64 reference rounded to e4m3
+    passes the bar against itself, the largest output sits at 400 under a
+    scale that is no power of two, and every control is rejected."""
+    import _e4m3_ref
+    o = kb.stream8_operands(form, B)
+    want, bnd = kb.stream8_bar(o)
+    assert abs(float(want.max()) - 400.0) < 1e-3 and o["out_scale"] != 2.0 ** round(math.log2(o["out_scale"]))
+    assert bool((o["ref"][0] < 0).any())  # the ReLU has something to do
+    got = _e4m3_ref.round_bytes(want.float()).view(torch.float8_e4m3fn).double()
+    ratio, _ = kb.assert_close(got, want, bnd, f"{form} B={B} rounded reference", l2=kb.L2_E4M3)
+    assert ratio > 0.5  # the bar is e4m3's own roundoff, not a loose multiple of it
+    controls = kb.stream8_controls(form, o)
+    assert [n for n, _ in controls] == [("seam taps" if kb.STREAM8_FORMS[form][4] else "border taps"), "chunk swap"] + \
+        (["batch shift"] if B > 1 else [])
+    for name, wrong in controls:
+        kb.assert_rejects(got, kb.stream8_bar(o, wrong)[0], bnd, f"{form} B={B} {name}")
+
+
+def test_border_taps_s2_halo_row():
+    """fault_border_taps_s2(kh=0): only output row r changes, by the kh = 0
+    taps on image row 2 r - 1; the default is the kh = 1 fault as before."""
+    o = kb.stream8_operands("28x28x256s2", 1)
+    ref, x, w = o["ref"][0], o["x"], o["weff"]
+    wrong = kb.fault_border_taps_s2(ref, x, w, at=13, kh=0)
+    assert torch.equal(wrong[:, :, :7], ref[:, :, :7]) and torch.equal(wrong[:, :, 8:], ref[:, :, 8:])
+    w0 = w.clone()
+    w0[:, :, 0] = 0
+    assert torch.allclose(wrong[:, :, 7], F.conv2d(x, w0, o["bias"], 2, 1)[:, :, 7], rtol=0, atol=1e-9)
+    w1 = w.clone()
+    w1[:, :, 1] = 0
+    d = kb.fault_border_taps_s2(ref, x, w, at=14)
+    assert torch.equal(d[:, :, :7], ref[:, :, :7]) and torch.equal(d[:, :, 8:], ref[:, :, 8:])
+    assert torch.allclose(d[:, :, 7], F.conv2d(x, w1, o["bias"], 2, 1)[:, :, 7], rtol=0, atol=1e-9)
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("form", list(kb.STREAM8_FORMS))
+def test_stream8_exact_operands(form, B):
+    """The exact test's conditions on the reference alone: every value inside
+    the kernel is exact in fp32 at both output scales, out_scale = 2 keeps
+    every output below 448 with negatives and grid ties among them, the
+    saturating scale puts a share of them past 448 and below -448, and every
+    control changes the expected bytes."""
+    o = kb.stream8_operands(form, B, exact=True)
+    ref, mag = o["ref"]
+    for t in (o["x"], o["w"], o["bias"]):
+        assert torch.equal(t, t.round())
+    assert float(mag.max()) / kb.STREAM8_SAT_SCALE < 2 ** 24 and set(o["alpha"].tolist()) == {0.5, 1.0, 2.0}
+    assert bool((o["w"].abs().sum((0, 1)) > 0).all())  # every tap is used
+    v = ref / o["out_scale"]
+    assert torch.equal(v.float().double(), v) and float(v.abs().max()) < 448 and bool((v < 0).any())
+    assert bool((v[(v > 8) & (v < 16)] % 1 == 0.5).any())  # ties of the e4m3 grid (step 1 in [8, 16))
+    vs = ref / kb.STREAM8_SAT_SCALE
+    over, under = (vs > 448).double().mean().item(), (vs < -448).double().mean().item()
+    print(f"{form} B={B}: {over:.3f} of the outputs past 448, {under:.3f} below -448 at the saturating scale")
+    assert 0.01 < over < 0.5 and 0.01 < under < 0.5
+    assert bool((kb.e4m3_bytes(vs)[vs > 448] == 0x7E).all()) and bool((kb.e4m3_bytes_signed(vs)[vs < -448] == 0xFE).all())
+    assert torch.equal(kb.e4m3_bytes_signed(v)[v >= 0], kb.e4m3_bytes(v)[v >= 0])
+    for name, wrong in kb.stream8_controls(form, o):
+        assert not torch.equal(kb.e4m3_bytes(wrong / o["out_scale"]), kb.e4m3_bytes(v)), name
