@@ -877,17 +877,27 @@ PYBIND11_MODULE(_C, m) {
   };
   m.def("plan_audit", [=](const std::string& arch, const py::dict& weights, const std::map<std::string, bool>& options,
                           int B, bool native, int num_cus, int num_classes, int image_size, int topk,
-                          bool tensor_in, bool features) {
+                          bool tensor_in, bool features, bool keep_acts) {
     std::vector<Op> ops;
     const EngineOptions opt = engine_options(options);
     PlanSpec spec;
     spec.B = B, spec.native = native, spec.side = opt.fork_ds;
-    spec.topk = topk, spec.tensor_in = tensor_in, spec.features = features;
+    spec.topk = topk, spec.tensor_in = tensor_in, spec.features = features, spec.keep_acts = keep_acts;
     const auto lines = Engine::plan_audit(arch, to_weight_map(weights), opt, spec, num_cus, &ops, num_classes, image_size);
     return py::make_tuple(plan_list(lines), op_list(ops));
   }, py::arg("arch"), py::arg("weights"), py::arg("options") = std::map<std::string, bool>{}, py::arg("B") = 256,
      py::arg("native") = true, py::arg("num_cus") = 256, py::arg("num_classes") = 1000, py::arg("image_size") = 224,
-     py::arg("topk") = 1, py::arg("tensor_in") = false, py::arg("features") = false);
+     py::arg("topk") = 1, py::arg("tensor_in") = false, py::arg("features") = false, py::arg("keep_acts") = false);
+  // host-only: every activation's (H, W, C, f32, e4m3, per-channel scales) as the graph marks them (scales uncalibrated)
+  m.def("shape_audit", [](const std::string& arch, const py::dict& weights, const std::map<std::string, bool>& options,
+                          int num_classes, int image_size) {
+    py::list out;
+    for (const auto& [s, chan] : Engine::shape_audit(arch, to_weight_map(weights), engine_options(options), num_classes,
+                                                     image_size))
+      out.append(py::make_tuple(s.H, s.W, s.C, s.f32, s.fp8, chan));
+    return out;
+  }, py::arg("arch"), py::arg("weights"), py::arg("options") = std::map<std::string, bool>{},
+     py::arg("num_classes") = 1000, py::arg("image_size") = 224);
   auto request = [](uintptr_t data, int B, int Hin, int Win, int k, uintptr_t idx, uintptr_t prob, uintptr_t logits,
                     uintptr_t features, bool l2norm, bool tensor = false, TensorDType dt = TensorDType::F32,
                     bool channels_last = false) {
@@ -977,12 +987,17 @@ PYBIND11_MODULE(_C, m) {
              auto s = e.activation_shape(id);
              return py::make_tuple(s.fp8, s.scale);
            })
-      .def("plan", [=](const Engine& e, int B, int Hin, int Win, int topk, bool tensor_in, bool features) {
+      // the per-channel e4m3 scales of a stored activation (empty: one per-tensor scale, activation_quant)
+      .def("activation_cscale", [](const Engine& e, int id) { return e.activation_shape(id).cscale; })
+      // keep_acts: the plan an eager forward runs (every activation stored); default: the captured graph's
+      .def("plan", [=](const Engine& e, int B, int Hin, int Win, int topk, bool tensor_in, bool features,
+                       bool keep_acts) {
         // planning reads no buffer: any non-null features pointer asks for the Embed step
-        const PlanSpec spec = e.spec_for(request(0, B, Hin, Win, topk, 0, 0, 0, features ? 1 : 0, false, tensor_in), false);
+        const PlanSpec spec =
+            e.spec_for(request(0, B, Hin, Win, topk, 0, 0, 0, features ? 1 : 0, false, tensor_in), keep_acts);
         return plan_list(e.plan_lines(e.plan(spec)));
       }, py::arg("B"), py::arg("Hin"), py::arg("Win"), py::arg("topk") = 1, py::arg("tensor_in") = false,
-         py::arg("features") = false)
+         py::arg("features") = false, py::arg("keep_acts") = false)
       .def_property_readonly("feature_dim", &Engine::feature_dim)
       .def_property_readonly("num_cus", &Engine::num_cus)
       .def_property_readonly("num_activations", &Engine::num_activations)

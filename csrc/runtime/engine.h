@@ -301,6 +301,11 @@ class Engine {
                                           std::vector<Op>* engine_ops = nullptr, int num_classes = 1000,
                                           int image_size = 224);
   std::vector<PlanLine> plan_lines(const std::vector<Step>& steps) const;
+  // Host-only like plan_audit: every activation's shape and dtype as the graph marks it, and whether it gets
+  // per-channel e4m3 scales (the scales themselves are calibrated on a device).
+  static std::vector<std::pair<ActShape, bool>> shape_audit(const std::string& arch, const WeightMap& weights,
+                                                            const EngineOptions& options, int num_classes = 1000,
+                                                            int image_size = 224);
   void* weight_arena() const { return warena_; }
 
   const std::string& arch() const { return arch_; }

@@ -718,4 +718,13 @@ std::vector<Engine::PlanLine> Engine::plan_audit(const std::string& arch, const 
   return e.plan_lines(e.plan(spec));
 }
 
+std::vector<std::pair<ActShape, bool>> Engine::shape_audit(const std::string& arch, const WeightMap& weights,
+                                                           const EngineOptions& options, int num_classes,
+                                                           int image_size) {
+  Engine e(HostOnly{}, arch, weights, num_classes, image_size, options);
+  std::vector<std::pair<ActShape, bool>> out;
+  for (size_t i = 0; i < e.shapes_.size(); ++i) out.emplace_back(e.shapes_[i], i < e.chan_act_.size() && e.chan_act_[i]);
+  return out;
+}
+
 }  // namespace dmlc

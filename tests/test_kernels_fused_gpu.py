@@ -443,6 +443,32 @@ def test_head_pooled(gpu, C, splits):
         _check_top1_kernel(out)
 
 
+@pytest.mark.parametrize("N,B,splits", [(520, 32, 0), (100, 1, 16), (100, 17, 16)])
+def test_head_pooled_empty_splits(gpu, N, B, splits):
+    """Fewer 16-class tiles than the splits can share out: the merge meets partials of splits that own no class
+    (sum == 0). N = 520: 33 tiles in 16 splits of 3, splits 11..15 empty; N = 100: 7 tiles, splits 7..15 empty.
+    The top class sits once in the first split and once in the last split that has classes (its last class, in
+    the partial tile)."""
+    C = 512
+    cus = torch.cuda.get_device_properties(gpu).multi_processor_count
+    ns = splits or dmlc.native().head_pooled_splits(B, N, cus)
+    assert ns == 16, ns
+    tiles = (N + 15) // 16
+    per = -(-tiles // ns)
+    last = (tiles - 1) // per  # the last split that owns classes
+    assert last < ns - 1, "no empty split"
+    for top in (5, N - 1):
+        assert top // (16 * per) == (0 if top == 5 else last)
+        x, w, bias, wp = _head_operands(B, 1, C, N, seed=130 + B)
+        bias[top] = 8.0  # the top class of every image, the others still count in the softmax sum
+        p = x[:, 0]
+        out = ops.head(p.to(gpu), wp.to(gpu), N, bias.to(gpu), pooled=True, splits=splits)
+        _, idx, _ = _check_head(out, p.double(), p.double().abs(), w, bias, C,
+                                f"head_pooled N={N} B={B} splits={ns} top={top}", B)
+        assert idx.tolist() == [top] * B
+        _check_top1_kernel(out)
+
+
 @pytest.mark.parametrize("ties", [(3, 7), (3, 900)], ids=["one tile", "across splits"])
 def test_head_ties_go_to_the_lower_class(gpu, ties):
     N, C = 1000, 512
