@@ -219,7 +219,7 @@ PYBIND11_MODULE(_C, m) {
           conv1x1(a, num_cus > 0 ? num_cus : device_cus(), S(stream));  // num_cus sizes the persistent grid
           return;
         }
-        if (tile == kConv1x1Tile + 2) {  // fully connected (fc_gemm.hip); split_k 0: fc_gemm_splits
+        if (tile == kConv1x1Tile + 2) {  // fully connected (fc.hip); split_k 0: fc_gemm_splits
           a.tile = -1;
           hipDeviceProp_t prop;
           int dev = 0;

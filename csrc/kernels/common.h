@@ -151,6 +151,15 @@ __device__ __forceinline__ int xswz(int K) {
     return ((K >> 1) & 3) << 1;
 }
 
+// Byte offset of 16-B chunk c (0..7) of row r in an LDS region of 128-B rows
+// whose chunks are XOR-swizzled by row (fc_kernels.h's stages, sim_topk.hip's).
+__device__ __forceinline__ int swz128(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
+
+// One fp8 MFMA operand (32 e4m3 bytes) from its two 16-B halves as loaded.
+__device__ __forceinline__ v8i e4m3x32(uint4 lo, uint4 hi) {
+  return v8i{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+}
+
 // ---- waits and barriers
 //
 // For the memory operations the compiler does not track (the LDS-DMA and

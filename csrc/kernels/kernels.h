@@ -82,7 +82,7 @@ void conv2d_igemm(const ConvArgs& a, hipStream_t s);
 // The split-K reduction (+ bias, residual, ReLU, bf16 / fp32 out) of `splits`
 // fp32 partial slices [splits][M][Npad] in a.ws.
 void splitk_reduce(const ConvArgs& a, long M, int splits, hipStream_t s);
-// Fully connected layers at M = B <= 256 (fc_gemm.hip): all rows x 128
+// Fully connected layers at M = B <= 256 (fc.hip, fc_kernels.h): all rows x 128
 // columns x one K slice per workgroup, tiles through a 3-slot LDS-DMA ring,
 // fp32 partials reduced by splitk_reduce (so a.ws is required even at 1 slice).
 bool fc_gemm_supported(const ConvArgs& a);
@@ -466,14 +466,14 @@ void head_pooled(const void* pooled, const void* w, const float* bias, int B, in
                  float* logits, int32_t* idx, float* prob, void* ws, size_t ws_bytes, int num_cus, hipStream_t s,
                  int ns_override = 0, int ko = 0);
 
-// Fully-connected layer at small batch (fc_small.hip): y[b][n] = act(x[b] .
+// Fully-connected layer at small batch (fc.hip, fc_kernels.h): y[b][n] = act(x[b] .
 // w[n] + bias[n]) for B <= 16 as a weight-streaming MFMA GEMV; x bf16
 // [B, ldx], w bf16 [Npad, ldw], y bf16 / fp32 [B, ldo].
 bool fc_small_supported(int B, int K, int ldx, int ldw);
 void fc_small(const void* x, int ldx, const void* w, int ldw, const float* bias, void* y, int ldo, bool out_f32,
               int B, int K, int N, int Npad, bool relu, hipStream_t s);
 
-// e4m3 fully connected layers (fc8.hip: the alexnet_fp8 classifier). Codes are
+// e4m3 fully connected layers (fc8.hip, fc_kernels.h: the alexnet_fp8 classifier). Codes are
 // OCP e4m3 bytes; y = act((sum_k cx[b][k] cw[n][k]) alpha[n] + bias[n]) as
 // bf16, fp32 (out_f32) or e4m3(y out_inv_scale), saturating (out_fp8).
 // quant_e4m3: bf16 rows x [B, K] (dense) -> y = e4m3(x inv_scale), saturating

@@ -17,7 +17,7 @@
 //
 // sim_topk_kernel. A workgroup owns one block of <= 256 queries and one
 // slice of the gallery: contiguous whole tiles of 128 rows, about one
-// workgroup per CU. fc_gemm.hip's loop with the operands' roles swapped:
+// workgroup per CU. fc_kernels.h's fc_gemm loop with the operands' roles swapped:
 //
 //  * a stage is one K block (64) of the tile's 128 gallery rows (16 KB) and of
 //    the 256 queries (32 KB, L2-resident, re-read per tile), brought to a
@@ -118,9 +118,6 @@ constexpr int kMaxD = 4096;
 static_assert(kLds <= 160 * 1024, "LDS per CU");
 static_assert(kMaxTopK == 16, "list rows of 16 entries");
 
-// 16-B chunk c (0..7) of a 128-B LDS row r
-__device__ __forceinline__ int st_off(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
-
 // (s, n) sorts before (ps, pn): the larger score, the lower row among equals
 __device__ __forceinline__ bool sorts_before(float s, int n, float ps, int pn) {
   return s > ps || (s == ps && n < pn);
@@ -195,7 +192,7 @@ __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const sim_elem<FP8>* _
   }
   lgkm_wait();
 
-  // Staging (fc_gemm.hip's): LDS position p = 64 i + l of a region holds row
+  // Staging (fc_kernels.h's): LDS position p = 64 i + l of a region holds row
   // p >> 3, physical chunk p & 7 = logical chunk (p & 7) ^ (row & 7). The
   // gallery region is 16 instructions (2 a wave), the query region 32 (4 a
   // wave; those whose 8 rows all lie past Bq are skipped). Every wait is
@@ -254,9 +251,7 @@ __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const sim_elem<FP8>* _
       if constexpr (FP8) {
         // the whole K block in one MFMA per fragment pair: chunks fq and fq + 4 of each row
         auto frag = [&](const char* region, int row) __attribute__((always_inline)) {
-          const uint4 lo = *(const uint4*)(region + st_off(row, fq));
-          const uint4 hi = *(const uint4*)(region + st_off(row, fq + 4));
-          return v8i{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+          return e4m3x32(*(const uint4*)(region + swz128(row, fq)), *(const uint4*)(region + swz128(row, fq + 4)));
         };
         v8i gfr[8], qfr[2];
 #pragma unroll
@@ -275,10 +270,10 @@ __global__ __launch_bounds__(512, 1) void sim_topk_kernel(const sim_elem<FP8>* _
           if (kb * kKB + 32 * kk < D) {  // (uniform)
             bf16x8 gfr[8], qfr[2];
 #pragma unroll
-            for (int gf = 0; gf < 8; ++gf) gfr[gf] = *(const bf16x8*)(base + st_off(16 * gf + fr, 4 * kk + fq));
+            for (int gf = 0; gf < 8; ++gf) gfr[gf] = *(const bf16x8*)(base + swz128(16 * gf + fr, 4 * kk + fq));
 #pragma unroll
             for (int qf = 0; qf < 2; ++qf)
-              qfr[qf] = *(const bf16x8*)(base + kGB + st_off(32 * wave + 16 * qf + fr, 4 * kk + fq));
+              qfr[qf] = *(const bf16x8*)(base + kGB + swz128(32 * wave + 16 * qf + fr, 4 * kk + fq));
 #pragma unroll
             for (int gf = 0; gf < 8; ++gf)
 #pragma unroll

@@ -133,7 +133,7 @@ struct EngineOptions {
                                  // walking its rows (conv3x3_s2rows.hip), B >= 0.7 x CUs
   bool rows28 = true;            // layer2's stride-1 convs the same way (conv3x3_rows28.hip), B >= 0.7 x CUs
   bool stem_roles = true;        // u8 stem: one workgroup per image with MFMA / helper waves once B >= CUs
-  bool fc_gemm = true;           // fully connected layers at B <= 256 on fc_gemm.hip (else the implicit GEMM)
+  bool fc_gemm = true;           // fully connected layers at B <= 256 on fc.hip's fc_gemm (else the implicit GEMM)
   bool stem_dense = true;        // ... with the dense-K weight order (5 K steps a fragment instead of 7)
   bool bigtile = true;           // 8-wave big-tile split-K convs where picked (not on the ResNet18 b256 path)
   bool conv1x1 = true;           // weight-stationary 1x1 convs (conv1x1.hip: ResNet50 bottlenecks)
@@ -145,7 +145,7 @@ struct EngineOptions {
   bool fused_head = true;        // avgpool + fc + softmax / top-1 in one kernel (head.hip)
   bool direct13 = true;          // AlexNet's 13x13 3x3 convs with the image resident in LDS (conv_direct.hip)
   bool direct27 = true;          // AlexNet's 5x5 conv on 27x27x64 the same way (conv_direct.hip)
-  bool fc_small = true;          // weight-streaming GEMV for fc layers at B <= 16 (fc_small.hip)
+  bool fc_small = true;          // weight-streaming GEMV for fc layers at B <= 16 (fc.hip's fc_small)
   // e4m3 fc layers (alexnet_fp8's classifier.1 / .4) on fc8.hip: fc_small8 at B <= 16, fc_gemm8 at B <= 256
   // (off, and above 256: the e4m3 implicit GEMM)
   bool fc8 = true;

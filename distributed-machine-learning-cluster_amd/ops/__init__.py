@@ -83,7 +83,7 @@ def stem_image(x_nhwc3: torch.Tensor, pad: int, row_width: int) -> torch.Tensor:
 
 def fc(x: torch.Tensor, w_packed: torch.Tensor, cout: int, bias: torch.Tensor | None = None, relu: bool = False,
        out_f32: bool = False, splits: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
-    """Fully connected layer at M <= 256 rows on fc_gemm.hip: x bf16 [M, K]
+    """Fully connected layer at M <= 256 rows on fc.hip's fc_gemm: x bf16 [M, K]
     (K = w_packed.shape[1], a multiple of 64), w_packed [Npad, K] (Npad % 128
     == 0) -> [M, cout] bf16 (fp32 with out_f32). splits: K slices (0: the
     engine's choice), fp32 partials reduced with the bias and ReLU. ``out``:
@@ -958,7 +958,7 @@ def conv3x3_13(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, relu
 
 def fc_small(x: torch.Tensor, w_packed: torch.Tensor, n: int, bias: torch.Tensor, relu: bool = False,
              out_f32: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
-    """Fully connected layer at B <= 16 rows (fc_small.hip): act(x . w[n] +
+    """Fully connected layer at B <= 16 rows (fc.hip's fc_small): act(x . w[n] +
     bias[n]). x bf16 [B, K] with unit column stride (its row stride may exceed
     K: a column slice of a wider activation), K % 32 == 0; w_packed bf16
     [Npad, ldw] with ldw >= K and Npad >= n rounded up to 16. Returns [B, n]

@@ -986,7 +986,7 @@ def case_seed(cases, name):
     return 500 + [c[1:3] for c in cases].index(key)
 
 
-# ---------------------------------------------------------------- fc_gemm.hip
+# ---------------------------------------------------------------- fc.hip (fc_gemm)
 FC_KB = 64      # K block
 FC_RING = 3     # LDS slots
 FC_BN = 128     # columns per workgroup

@@ -456,7 +456,7 @@ def test_weight_stationary_rows_match_stream(gpu, option):
 @pytest.mark.parametrize("B", [1, 5, 16])
 def test_alexnet_small_batch_fc_matches_reference(gpu, B):
     """Query-sized AlexNet batches run the classifier on the weight-streaming
-    split-K GEMV (fc_small.hip): vs fp32 torch.nn, and vs the throughput
+    split-K GEMV (fc.hip's fc_small): vs fp32 torch.nn, and vs the throughput
     path (options fc_small=False: the implicit GEMM) on the same inputs."""
     model = build("alexnet", seed=51, randomize_bn=True)
     sd = state_dict_f32(model)

@@ -3,7 +3,7 @@ as their yardstick and which test_kernels_gpu.py / test_fp8_gpu.py judge by a
 relative-L2 norm alone: conv_igemm.hip (11 tiles, split-K with
 splitk_reduce, persistent grids, the packed-RGB stem, six e4m3
 instantiations), conv_bigtile.hip (256x256 / 256x128 tiles with split-K slabs,
-the persistent form) and fc_gemm.hip.
+the persistent form) and fc.hip's fc_gemm.
 
 As in test_kernels_resnet50_gpu.py every output is compared element-wise with
 a float64 reference on the same (bf16 / e4m3) operands under the derived bar

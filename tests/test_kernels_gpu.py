@@ -439,7 +439,7 @@ def test_conv3x3_rows(gpu, B, strip, res):
                                                    (256, 4096, 1000, False, True, 0), (3, 9216, 4096, True, False, 0),
                                                    (200, 1024, 256, True, False, 1), (64, 4096, 1000, False, True, 4)])
 def test_fc_gemm(gpu, M, K, N, relu, f32, splits):
-    """Fully connected layers on fc_gemm.hip (AlexNet's classifier shapes at
+    """Fully connected layers on fc.hip's fc_gemm (AlexNet's classifier shapes at
     B = 256, a query batch, a ragged M, one and several K slices) vs torch
     fp32 on the same bf16 operands; the zero-page rows past M stay out of
     the result."""

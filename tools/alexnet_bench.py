@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """AlexNet forward latency at query batch sizes (graph replay, host-timed
 including the D2H of the answers) and the classifier's share of it; run
-under rocprofv3 --kernel-trace for per-kernel times (fc_small_kernel per
+under rocprofv3 --kernel-trace for per-kernel times (fc_small_kernel<false> per
 classifier layer vs its HBM floor: 75.5 / 33.6 / 8.2 MB of bf16 weights).
 usage: python tools/alexnet_bench.py [--batches 1,8,16] [--iters 200]"""
 import argparse
