@@ -500,6 +500,31 @@ PYBIND11_MODULE(_C, m) {
         py::arg("wd") = 0, py::arg("alpha_d") = 0, py::arg("bias_d") = 0, py::arg("yd") = 0,
         py::arg("out_inv_scale_d") = 0.f);
   m.def("conv3x3_stream8_block_supported", &conv3x3_stream8_block_supported);
+  m.def("conv_small8_supported", &conv_small8_supported, py::arg("H"), py::arg("W"), py::arg("CI"), py::arg("CO"),
+        py::arg("stride"), py::arg("res") = false, py::arg("ds") = false);
+  m.def("conv_small8_pick_mf", &conv_small8_pick_mf, py::arg("B"), py::arg("H"), py::arg("W"), py::arg("CI"),
+        py::arg("CO"), py::arg("stride"), py::arg("ds"), py::arg("num_cus"));
+  m.attr("kSmallConv8MaxB") = kSmallConv8MaxB;
+  m.def("small_conv8_set_max_b", &small_conv8_set_max_b);
+  m.def("conv_small8", [](uintptr_t x, uintptr_t wf, uintptr_t alpha, uintptr_t bias, uintptr_t y, uintptr_t zero,
+                          int B, int H, int W, int CI, int CO, int stride, bool relu, float out_inv_scale, int mf,
+                          uintptr_t stream, uintptr_t res, float res_scale, uintptr_t wd, uintptr_t alpha_d,
+                          uintptr_t bias_d, uintptr_t yd, float out_inv_scale_d) {
+    Stream8Block blk;
+    blk.res = P<void>(res);
+    blk.res_scale = res_scale;
+    blk.wd = P<void>(wd);
+    blk.alpha_d = P<float>(alpha_d);
+    blk.bias_d = P<float>(bias_d);
+    blk.yd = P<void>(yd);
+    blk.out_inv_scale_d = out_inv_scale_d;
+    conv_small8(P<void>(x), P<void>(wf), P<float>(alpha), P<float>(bias), P<void>(y), P<void>(zero), B, H, W, CI, CO,
+                stride, relu, out_inv_scale, mf, S(stream), &blk);
+  }, py::arg("x"), py::arg("wf"), py::arg("alpha"), py::arg("bias"), py::arg("y"), py::arg("zero"), py::arg("B"),
+        py::arg("H"), py::arg("W"), py::arg("CI"), py::arg("CO"), py::arg("stride"), py::arg("relu"),
+        py::arg("out_inv_scale"), py::arg("mf"), py::arg("stream") = 0, py::arg("res") = 0,
+        py::arg("res_scale") = 1.f, py::arg("wd") = 0, py::arg("alpha_d") = 0, py::arg("bias_d") = 0,
+        py::arg("yd") = 0, py::arg("out_inv_scale_d") = 0.f);
   m.def("conv3x3_s2rows_supported", &conv3x3_s2rows_supported);
   m.def("conv3x3_s2rows128_supported", &conv3x3_s2rows128_supported);
   m.def("conv3x3_s2rows128", [](uintptr_t x, uintptr_t wf, uintptr_t bias, uintptr_t y, int B, bool relu,

@@ -343,6 +343,19 @@ void conv3x3_stream8(const void* x, const void* wf, const float* alpha, const fl
                      int B, int Hin, int Win, int Cin, int Cout, int stride, bool relu, float out_inv_scale,
                      hipStream_t s, const Stream8Block* blk = nullptr);
 void conv3x3_stream8_set_variant(int v);  // test hook (0 = the defaults; 4: 7-row strips at layer2.0.conv2)
+// Query-batch e4m3 3x3/p1 conv (conv_small8.hip), stride 1 or 2, for B <= a
+// few images: one launch per conv, no split-K. Operands and arithmetic are
+// conv3x3_stream8's (and Stream8Block's: res at stride 1 with CO == CI; wd /
+// alpha_d / bias_d / yd / out_inv_scale_d at stride 2), wf / wd the same
+// conv3x3_stream8_frag_offset copies; H and W are runtime values, CI in {128,
+// 256, 512}, CO == CI or 2 CI at stride 2. A lane stores the 4 channels of one
+// N fragment: y, res and yd need 4-B alignment only. mf: pixel fragments of 16
+// per workgroup (1, 2 or 4; conv_small8_pick_mf).
+bool conv_small8_supported(int H, int W, int CI, int CO, int stride, bool res, bool ds);
+int conv_small8_pick_mf(int B, int H, int W, int CI, int CO, int stride, bool ds, int num_cus);
+void conv_small8(const void* x, const void* wf, const float* alpha, const float* bias, void* y, const void* zero,
+                 int B, int H, int W, int CI, int CO, int stride, bool relu, float out_inv_scale, int mf,
+                 hipStream_t s, const Stream8Block* blk = nullptr);
 // Stride 2 may also compute the block's 1x1/s2 downsample conv (wd [Cout,
 // Cin], bias bd, no ReLU) from the same resident input into yd.
 void conv3x3_stream(const void* x, const void* w, const float* bias, const void* res, void* y, const void* zero,

@@ -42,6 +42,7 @@ bool EngineOptions::set(const std::string& name, bool v) {
       {"fc8", &EngineOptions::fc8},
       {"igemm_small_m", &EngineOptions::igemm_small_m},
       {"small_conv", &EngineOptions::small_conv},
+      {"small_conv8", &EngineOptions::small_conv8},
   };
   for (const auto& f : fields)
     if (name == f.first) {
@@ -745,6 +746,7 @@ void Engine::run_ops(const std::vector<Step>& steps, const Request& req, hipStre
                    Lp->stride, Lp->relu, st.count, cs, D ? W(D->wf_off) : nullptr, D ? F(D->b_off) : nullptr,
                    D ? acts_[d->out] : nullptr);
         break;
+      case Kernel::Small8:
       case Kernel::Stream8: {
         Stream8Block blk;  // a basic block's residual, or its downsample from the same launch
         if (res) {
@@ -758,8 +760,12 @@ void Engine::run_ops(const std::vector<Step>& steps, const Request& req, hipStre
           blk.yd = acts_[d->out];
           blk.out_inv_scale_d = 1.f / shapes_[d->out].scale;
         }
-        conv3x3_stream8(acts_[op.in], W(Lp->wf_off), F(Lp->a_off), F(Lp->b_off), acts_[op.out], zero_, B, isp->H,
-                        isp->W, isp->C, Lp->cout, Lp->stride, Lp->relu, 1.f / shapes_[op.out].scale, cs, &blk);
+        if (st.kernel == Kernel::Small8)  // query batches: the same operands, st.count = mf
+          conv_small8(acts_[op.in], W(Lp->wf_off), F(Lp->a_off), F(Lp->b_off), acts_[op.out], zero_, B, isp->H, isp->W,
+                      isp->C, Lp->cout, Lp->stride, Lp->relu, 1.f / shapes_[op.out].scale, st.count, cs, &blk);
+        else
+          conv3x3_stream8(acts_[op.in], W(Lp->wf_off), F(Lp->a_off), F(Lp->b_off), acts_[op.out], zero_, B, isp->H,
+                          isp->W, isp->C, Lp->cout, Lp->stride, Lp->relu, 1.f / shapes_[op.out].scale, cs, &blk);
         break;
       }
       case Kernel::Rows28:

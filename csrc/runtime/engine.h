@@ -97,6 +97,12 @@ struct Op {
 // A/B-timed (profiles/). Python: InferenceEngine(..., options={"fused_block":
 // False}); the names are the field names.
 constexpr int kSmallConvMaxB = 4;  // largest batch on the query-batch conv path
+// ... on the e4m3 one (small_conv8): faster than the e4m3 implicit GEMM for all three fp8
+// ResNets at every swept batch up to 32 (profiles/small8.txt)
+constexpr int kSmallConv8MaxB = 32;
+// A/B hook (tools/small8_bench.py times larger batches on the e4m3 query-batch
+// path): the bound the planner uses, 0 = kSmallConv8MaxB
+void small_conv8_set_max_b(int b);
 constexpr int kPoolThenHeadB = 32;  // from this batch on an unfused-pool head pools once, then head_pooled
 
 struct EngineOptions {
@@ -109,7 +115,11 @@ struct EngineOptions {
   // query batches (B <= kSmallConvMaxB): every 3x3 conv (+ its block's 1x1/s2
   // downsample) as one conv_small.hip launch, no split-K reduction kernels
   bool small_conv = true;
-  bool fused_stem = true;        // conv1 + BN + ReLU + maxpool in one kernel (stem_pool.hip)
+  // the same for the e4m3-in / e4m3-out 3x3 convs of the *_fp8 ResNets (B <=
+  // kSmallConv8MaxB, conv_small8.hip) instead of the e4m3 implicit GEMM; off
+  // until the default plans are re-recorded with profiles/small8.txt in hand
+  bool small_conv8 = false;
+  bool fused_stem = true;       // conv1 + BN + ReLU + maxpool in one kernel (stem_pool.hip)
   bool fused_preprocess = true;  // SxS u8 images straight into the fused stem (no preprocess pass)
   bool row_conv = true;          // direct row-streaming 3x3 convs (conv3x3_rows.hip) for 56x56x64
   bool rows_wreg = true;         // ... with register-streamed weights, 2 workgroups per CU
@@ -209,7 +219,7 @@ enum class Kernel {
   AlexStem, StemPoolU8, StemPool, FcSmall, Conv1x1Cat, Conv1x1Chain, Bottleneck56, Bottleneck56Head, Block,
   S2Rows, S2Rows128, Stream, Stream8, Rows28, Rows, Small, Direct13, Direct27, Conv1x1, BigTile, Igemm, FcGemm,
   HeadPooled, HeadFused, AvgPoolGlobal, AvgPoolAdaptive, MaxPool, Preprocess, PackTensor, SoftmaxTop1, SoftmaxTopK,
-  Embed, QuantE4m3, FcSmall8, FcGemm8
+  Embed, QuantE4m3, FcSmall8, FcGemm8, Small8
 };
 const char* kernel_name(Kernel k);
 
@@ -217,7 +227,7 @@ struct Step {
   Kernel kernel = Kernel::None;
   int first_op = 0, n_ops = 1;  // ops_[first_op .. first_op + n_ops) are done by this step
   // a block's downsample op this launch computes: written to its activation
-  // (S2Rows, Stream, Small), or as extra K steps with no activation written
+  // (S2Rows, Stream, Stream8, Small, Small8), or as extra K steps with no activation written
   // (Rows28: ds_into_conv2, Conv1x1Cat: ds_into_expand)
   int ds_op = -1;
   int pool_op = -1;      // pool op whose output the conv's epilogue writes (Stream, Direct13, Direct27)
@@ -225,7 +235,7 @@ struct Step {
   bool store_y = true;   // false: the last op's activation is not written (Stream with the pool fused, under a graph)
   bool side = false;     // runs on the side stream (fork_ds)
   int cfg = -1;          // BigTile: tile config
-  // Rows / StemPool / StemPoolU8: strip; Small: mf; BigTile / FcGemm / FcGemm8: K splits; SoftmaxTopK: k;
+  // Rows / StemPool / StemPoolU8: strip; Small / Small8: mf; BigTile / FcGemm / FcGemm8: K splits; SoftmaxTopK: k;
   // Embed: the pixels it averages (0: src_op's output is the feature row itself)
   int count = 0;
   int src_op = -1;       // Embed: the op whose output activation it reads

@@ -82,10 +82,15 @@ const char* kernel_name(Kernel k) {
       "Bottleneck56Head", "Block", "S2Rows", "S2Rows128", "Stream", "Stream8", "Rows28", "Rows", "Small", "Direct13",
       "Direct27", "Conv1x1", "BigTile", "Igemm", "FcGemm", "HeadPooled", "HeadFused", "AvgPoolGlobal",
       "AvgPoolAdaptive", "MaxPool", "Preprocess", "PackTensor", "SoftmaxTop1", "SoftmaxTopK", "Embed", "QuantE4m3",
-      "FcSmall8", "FcGemm8"};
-  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::FcGemm8 + 1, "one name per Kernel");
+      "FcSmall8", "FcGemm8", "Small8"};
+  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::Small8 + 1, "one name per Kernel");
   return names[(size_t)k];
 }
+
+namespace {
+int g_small_conv8_max_b = 0;  // small_conv8_set_max_b
+}
+void small_conv8_set_max_b(int b) { g_small_conv8_max_b = b; }
 
 // ---------------------------------------------------------------- planner
 // What to launch for one forward of B images: each conv op's kernel path
@@ -93,7 +98,7 @@ const char* kernel_name(Kernel k) {
 // launch swallows. Reads the graph, the layout pass's results (frag, cat_off,
 // npad) and num_cus_; no device state.
 struct Engine::Planner {
-  enum class Path { Stream, Rows, Rows28, Direct13, Direct27, OneByOne, BigTile, Igemm, Small, Stream8, Fc };
+  enum class Path { Stream, Rows, Rows28, Direct13, Direct27, OneByOne, BigTile, Igemm, Small, Stream8, Small8, Fc };
 
   const Engine& e;
   const std::vector<Op>& ops;
@@ -160,8 +165,15 @@ struct Engine::Planner {
     if (opt.direct13 && k3 && L.stride == 1 && L.frag == FragOrder::Stream &&
         conv3x3_13_supported(is.H, is.W, is.C, L.cout))
       return Path::Direct13;
+    // e4m3 in and out at query batches: one launch per conv (conv_small8.hip),
+    // a basic block's conv2 with its e4m3 residual
+    if (opt.small_conv8 && B <= (g_small_conv8_max_b > 0 ? g_small_conv8_max_b : kSmallConv8MaxB) && L.fp8 && !L.fc &&
+        L.kh == 3 && L.kw == 3 && L.pad == 1 && L.frag == FragOrder::Stream8 && shapes[op.out].fp8 &&
+        (op.res < 0 || (shapes[op.res].fp8 && shapes[op.res].cscale.empty())) &&
+        conv_small8_supported(is.H, is.W, is.C, L.cout, L.stride, op.res >= 0, false))
+      return Path::Small8;
     // e4m3 in and out (fp8_3x3_in): whole images per workgroup, once the batch
-    // fills the CUs (query batches: the e4m3 implicit GEMM)
+    // fills the CUs (query batches: the e4m3 implicit GEMM, or conv_small8 above)
     // (a basic block's conv2 with its e4m3 residual, and its channel-doubling
     // stride-2 conv1: the basic-block forms)
     if (L.fp8 && !L.fc && L.kh == 3 && L.kw == 3 && L.pad == 1 && L.frag == FragOrder::Stream8 &&
@@ -247,12 +259,17 @@ struct Engine::Planner {
     const Op& c = ops[oi + 1];
     const ConvLayer& D = convs[d.conv];
     const ConvLayer& L = convs[c.conv];
-    // e4m3 in and out: conv3x3_stream8's downsample phase (layer4.0 of resnet18_fp8 / resnet34_fp8)
-    if (D.fp8)
+    // e4m3 in and out: conv3x3_stream8's downsample phase (layer4.0 of resnet18_fp8 / resnet34_fp8), or
+    // conv_small8's centre-tap K-tiles
+    if (D.fp8) {
+      const ActShape& is = shapes[c.in];
       return d.in == c.in && !D.fc && D.kh == 1 && D.kw == 1 && D.stride == 2 && D.pad == 0 && !D.relu && d.res < 0 &&
-             D.cout == L.cout && c.res < 0 && D.frag == FragOrder::Stream8 && path[oi + 1] == Path::Stream8 &&
-             shapes[d.out].fp8 && shapes[d.out].cscale.empty() &&
-             conv3x3_stream8_block_supported(shapes[c.in].H, shapes[c.in].W, shapes[c.in].C, L.cout, L.stride, false, true);
+             D.cout == L.cout && c.res < 0 && D.frag == FragOrder::Stream8 && shapes[d.out].fp8 &&
+             shapes[d.out].cscale.empty() &&
+             ((path[oi + 1] == Path::Stream8 &&
+               conv3x3_stream8_block_supported(is.H, is.W, is.C, L.cout, L.stride, false, true)) ||
+              (path[oi + 1] == Path::Small8 && conv_small8_supported(is.H, is.W, is.C, L.cout, L.stride, false, true)));
+    }
     return d.in == c.in && D.plain_ds2() && !D.relu && d.res < 0 && D.cout == L.cout && L.stride == 2 &&
            !shapes[d.out].fp8 && !shapes[d.out].f32 &&
            (path[oi + 1] == Path::Stream || (path[oi + 1] == Path::Small && D.frag == FragOrder::Stream));
@@ -490,6 +507,11 @@ struct Engine::Planner {
         st.kernel = Kernel::Stream8;
         st.ds_op = ds;
         break;
+      case Path::Small8:
+        st.kernel = Kernel::Small8;
+        st.ds_op = ds;
+        st.count = conv_small8_pick_mf(B, is.H, is.W, is.C, L.cout, L.stride, ds >= 0, cus);
+        break;
       case Path::Rows28:
         st.kernel = Kernel::Rows28;
         if (ds_conv2 >= 0 && op.res == ops[ds_conv2].out) {
@@ -696,7 +718,7 @@ std::string Engine::step_detail(const Step& st) const {
   if (st.side) add("side");
   if (st.cfg >= 0) add("cfg=" + std::to_string(st.cfg));
   if (st.count > 0) {
-    const char* what = st.kernel == Kernel::Small ? "mf=" : st.kernel == Kernel::SoftmaxTopK ? "k=" : st.kernel == Kernel::Embed ? "hw=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm || st.kernel == Kernel::FcGemm8) ? "splits=" : "strip=";
+    const char* what = (st.kernel == Kernel::Small || st.kernel == Kernel::Small8) ? "mf=" : st.kernel == Kernel::SoftmaxTopK ? "k=" : st.kernel == Kernel::Embed ? "hw=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm || st.kernel == Kernel::FcGemm8) ? "splits=" : "strip=";
     add(what + std::to_string(st.count));
   }
   return d;

@@ -674,6 +674,50 @@ def conv3x3_stream8(x: torch.Tensor, w_q: torch.Tensor, alpha: torch.Tensor, bia
     return y if wd is None else (y, yd)
 
 
+def conv_small8(x: torch.Tensor, w_q: torch.Tensor, alpha: torch.Tensor, bias: torch.Tensor, relu: bool = True,
+                out_scale: float = 1.0, stride: int = 1, *, res: torch.Tensor | None = None, res_scale: float = 1.0,
+                wd: torch.Tensor | None = None, alpha_d: torch.Tensor | None = None,
+                bias_d: torch.Tensor | None = None, out_scale_d: float = 1.0, mf: int | None = None):
+    """Query-batch e4m3 3x3/p1 conv (conv_small8.hip), stride 1 or 2, on e4m3
+    NHWC [B,H,W,Cin] with Cin in {128, 256, 512}: conv3x3_stream8's operands
+    and arithmetic for any H x W and a few images, one launch. w_q: e4m3
+    [Cout, 9 Cin] (k = tap * Cin + c), Cout = Cin, or 2 Cin at stride 2.
+    ``res`` (stride 1, the output's shape) adds res * res_scale before the
+    ReLU; ``wd`` (stride 2: e4m3 [Cout, Cin], alpha_d, bias_d, out_scale_d)
+    also returns the block's 1x1/s2 downsample from the same launch: (y, yd).
+    mf: pixel fragments of 16 per workgroup (1, 2, 4; None: conv_small8_pick_mf)."""
+    _need_cuda(x, w_q, alpha, bias, res, wd, alpha_d, bias_d)
+    C = native()
+    if x.dim() != 4 or w_q.dim() != 2 or x.dtype != FP8:
+        raise ValueError("conv_small8: x is e4m3 NHWC, w_q e4m3 [Cout, 9 Cin]")
+    B, H, W, Cin = x.shape
+    cout = w_q.shape[0]
+    if w_q.shape[1] != 9 * Cin or not C.conv_small8_supported(H, W, Cin, cout, stride, res is not None, wd is not None):
+        raise ValueError("conv_small8: unsupported shape")
+    Ho, Wo = C.conv_out_dim(H, 3, stride, 1), C.conv_out_dim(W, 3, stride, 1)
+    if mf is None:
+        cus = torch.cuda.get_device_properties(x.device).multi_processor_count
+        mf = C.conv_small8_pick_mf(B, H, W, Cin, cout, stride, wd is not None, cus)
+    y = torch.empty(B, Ho, Wo, cout, dtype=FP8, device=x.device)
+    extra, yd = {}, None
+    if res is not None:
+        if tuple(res.shape) != tuple(y.shape):
+            raise ValueError("conv_small8: res has the output's shape")
+        extra.update(res=_ptr(_e4m3(res, "conv_small8: res")), res_scale=float(res_scale))
+    if wd is not None:
+        if tuple(wd.shape) != (cout, Cin) or alpha_d is None or bias_d is None:
+            raise ValueError("conv_small8: wd is e4m3 [Cout, Cin] with alpha_d, bias_d and out_scale_d")
+        yd = torch.empty_like(y)
+        wdf = stream8_weight_frag(_e4m3(wd, "conv_small8: wd"), cout)
+        extra.update(wd=_ptr(wdf), alpha_d=_ptr(_f32(alpha_d, cout, "alpha_d")),
+                     bias_d=_ptr(_f32(bias_d, cout, "bias_d")), yd=_ptr(yd), out_inv_scale_d=1.0 / out_scale_d)
+    wf = stream8_weight_frag(_e4m3(w_q, "conv_small8: w_q"), cout)
+    C.conv_small8(_ptr(x.contiguous()), _ptr(wf), _ptr(_f32(alpha, cout, "alpha")), _ptr(_f32(bias, cout, "bias")),
+                  _ptr(y), _ptr(_zero_page(x.device)), B, H, W, Cin, cout, stride, relu, 1.0 / out_scale, int(mf),
+                  _stream(), **extra)
+    return y if wd is None else (y, yd)
+
+
 def maxpool2d(x: torch.Tensor, k: int = 3, stride: int = 2, pad: int = 1) -> torch.Tensor:
     _need_cuda(x)
     C = native()

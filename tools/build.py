@@ -118,6 +118,7 @@ HIPCC_FILE_FLAGS = {
     # 215 / 189 / 250 VGPRs without packed ops, 224 / 183 / 250 with them, no scratch either way.
     "conv3x3_stream8_block.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "fc8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "conv_small8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 
