@@ -401,6 +401,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("alex_stem_u8", [](uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, int B, uintptr_t stream) {
     alex_stem_u8(P<uint8_t>(x), P<void>(w), P<float>(bias), P<void>(y), B, S(stream));
   }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("B"), py::arg("stream"));
+  m.def("alex_stem_rows_u8", [](uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, int B, uintptr_t stream) {
+    alex_stem_rows_u8(P<uint8_t>(x), P<void>(w), P<float>(bias), P<void>(y), B, S(stream));
+  });
   m.def("conv5x5_27_supported", &conv5x5_27_supported);
   m.def("conv5x5_27", [](uintptr_t x, uintptr_t wf, uintptr_t bias, uintptr_t y, uintptr_t zero, int B,
                          uintptr_t stream, uintptr_t ypool) {
@@ -549,6 +552,19 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("x"), py::arg("wf"), py::arg("bias"), py::arg("res"), py::arg("y"), py::arg("B"), py::arg("H"),
         py::arg("W"), py::arg("CI"), py::arg("CO"), py::arg("stride"), py::arg("relu"), py::arg("mf"),
         py::arg("stream"), py::arg("wdf") = 0, py::arg("bd") = 0, py::arg("yd") = 0);
+  m.def("conv_smallk_supported", &conv_smallk_supported, py::arg("H"), py::arg("W"), py::arg("CI"), py::arg("CO"),
+        py::arg("ks"), py::arg("pad"), py::arg("pool"));
+  m.def("conv_smallk_pick_mf", &conv_smallk_pick_mf, py::arg("B"), py::arg("H"), py::arg("W"), py::arg("CI"),
+        py::arg("CO"), py::arg("ks"), py::arg("num_cus"));
+  m.def("conv_smallk", [](uintptr_t x, uintptr_t wf, uintptr_t bias, uintptr_t y, int B, int H, int W, int CI, int CO,
+                          int ks, int pad, bool relu, bool pool, int mf, uintptr_t stream) {
+    conv_smallk(P<void>(x), P<void>(wf), P<float>(bias), P<void>(y), B, H, W, CI, CO, ks, pad, relu, pool, mf,
+                S(stream));
+  }, py::arg("x"), py::arg("wf"), py::arg("bias"), py::arg("y"), py::arg("B"), py::arg("H"), py::arg("W"),
+        py::arg("CI"), py::arg("CO"), py::arg("ks"), py::arg("pad"), py::arg("relu"), py::arg("pool"), py::arg("mf"),
+        py::arg("stream"));
+  m.def("small_alex_set_max_b", &small_alex_set_max_b);
+  m.attr("kSmallAlexMaxB") = kSmallAlexMaxB;
   m.def("conv3x3_rows28_supported", &conv3x3_rows28_supported);
   m.def("conv3x3_rows28", [](uintptr_t x, uintptr_t wf, uintptr_t bias, uintptr_t res, uintptr_t y, int B, bool relu,
                              uintptr_t stream, float out_inv_scale, uintptr_t xds, uintptr_t wds, uintptr_t bds) {

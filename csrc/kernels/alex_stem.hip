@@ -31,27 +31,17 @@
 //    chunks XOR-swizzled by pixel: conflict-free stores and reads); every
 //    second conv row the 3x3/s2 max of the three latest rows is stored as one
 //    pooled row (post-ReLU values are >= 0: bf16 max = unsigned 16-bit max).
-#include "common.h"
+#include "alex_stem_common.h"
 #include "kernels.h"
 
 namespace dmlc {
 
 namespace {
 
-typedef unsigned short ushort8 __attribute__((ext_vector_type(8)));
+using namespace alex;  // geometry, conv_off, convert_chunk: alex_stem_common.h
 
-constexpr int kS = 224;         // input image size
-constexpr int kHo = 55;         // conv output size
-constexpr int kPH = 27;         // pooled output size
-constexpr int kC = 64;          // output channels
-constexpr int kChunks = 114;    // paired chunks per padded row (228 padded pixels)
-constexpr int kRowB = 136 * 16; // staged paired row: chunks >= 114 stay zero (fragment padding reads up to 131)
 constexpr int kRing = 32;       // paired rows (power of two): 15 in use + 16 converted ahead
-constexpr int kKS = 17;         // K steps of 32 (68 chunks, 66 used)
-constexpr int kU8B = kS * 3;    // 672 bytes per raw image row
-constexpr int kU8Slot = 704;    // raw ring slot (16-B aligned)
 constexpr int kU8Ring = 32;     // raw rows: 8 converting + 16 in flight (DMA two iterations ahead)
-constexpr int kConvB = kHo * 128;  // one conv row [55][64] bf16
 constexpr int kConvRing = 8;    // conv rows: 3 pooled + 2 written per iteration
 constexpr size_t kLds = (size_t)kRing * kRowB + (size_t)kConvRing * kConvB + (size_t)kU8Ring * kU8Slot;
 
@@ -61,9 +51,6 @@ struct AlexStemArgs {
   const float* bias;   // [64]
   bf16* y;             // [B, 27, 27, 64]
 };
-
-// conv-ring byte offset of 16-B channel chunk c of pixel px
-__device__ __forceinline__ int conv_off(int px, int c) { return px * 128 + ((c ^ (px & 7)) << 4); }
 
 __global__ __launch_bounds__(512, 1) void alex_stem_kernel(AlexStemArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint4 smem[];
@@ -80,36 +67,6 @@ __global__ __launch_bounds__(512, 1) void alex_stem_kernel(AlexStemArgs a) {
   // chunks must read as finite zeros (they meet zero weights)
   for (int o = tid * 16; o < kRing * kRowB; o += 512 * 16) *(uint4*)(ring + o) = make_uint4(0, 0, 0, 0);
 
-  // paired chunk p of padded row pr from the raw ring (image row pr - 2,
-  // columns 2p-2, 2p-1 = bytes 6p-6 .. 6p-1): the exact values preprocess_u8
-  // would produce (imagenet_norm). Branch-free: two dword reads issued
-  // together (a byte read per value, each under its own branch and wait,
-  // was most of this kernel's time), the bytes picked by shifts, out-of-image
-  // values selected to zero.
-  auto convert_chunk = [&](int pr, int p) __attribute__((always_inline)) {
-    const int iy = pr - 2;
-    const bool row_in = iy >= 0 && iy < kS;
-    const int pc = p < 1 ? 1 : p > kChunks - 2 ? kChunks - 2 : p;  // in-row address for the edge chunks
-    const int start = 6 * pc - 6;                                  // byte offset, even
-    const uint32_t* src = (const uint32_t*)(raw + (pr % kU8Ring) * kU8Slot + (start & ~3));
-    const uint32_t d0 = src[0], d1 = src[1], d2 = src[2];
-    // 64-bit window starting at the first wanted byte
-    const uint64_t w = (start & 2) ? ((uint64_t)d2 << 48 | (uint64_t)d1 << 16 | (d0 >> 16))
-                                   : ((uint64_t)d1 << 32 | d0);
-    float v[8];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int ix = 2 * p - 2 + q;
-      const bool in = row_in && ix >= 0 && ix < kS;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float raw_v = (float)(uint32_t)((w >> (8 * (3 * q + c))) & 0xffu);
-        v[3 * q + c] = in ? imagenet_norm(c, raw_v) : 0.f;
-      }
-    }
-    v[6] = v[7] = 0.f;
-    *(uint4*)(ring + (pr & (kRing - 1)) * kRowB + p * 16) = pack8(v);
-  };
   // raw image row of padded row pr -> raw ring (LDS-DMA, one wave, 42 lanes)
   auto dma_row = [&](int pr) __attribute__((always_inline)) {
     const int iy = pr - 2;
@@ -156,7 +113,7 @@ __global__ __launch_bounds__(512, 1) void alex_stem_kernel(AlexStemArgs a) {
   __syncthreads();
   for (int it = tid; it < 23 * kChunks; it += 512) {
     const int pr = it / kChunks, p = it - pr * kChunks;
-    convert_chunk(pr, p);
+    convert_chunk<kU8Ring, kRing>(raw, ring, pr, p);
   }
   lgkm_wait();
   __syncthreads();
@@ -196,7 +153,7 @@ __global__ __launch_bounds__(512, 1) void alex_stem_kernel(AlexStemArgs a) {
     for (int it = tid; it < 8 * kChunks; it += 512) {
       const int q = it / kChunks, p = it - q * kChunks;
       const int pr = 4 * r0 + 23 + q;
-      if (r0 + 4 + (q >> 2) < kHo) convert_chunk(pr, p);
+      if (r0 + 4 + (q >> 2) < kHo) convert_chunk<kU8Ring, kRing>(raw, ring, pr, p);
     }
     // ---- conv rows r0, r0 + 1: 17 k-steps x 2 n-blocks each
 #pragma unroll

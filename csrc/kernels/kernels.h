@@ -306,6 +306,18 @@ void conv_small_set_mf(int mf);  // A/B override of the pick (0 = heuristic)
 void conv_small(const void* x, const void* wf, const float* bias, const void* res, void* y, int B, int H, int W,
                 int CI, int CO, int stride, bool relu, int mf, hipStream_t s, const void* wdf = nullptr,
                 const float* bd = nullptr, void* yd = nullptr);
+// Query-batch k x k / stride-1 conv of AlexNet's four feature convs
+// (conv_smallk.hip): 5x5 / pad 2 on 27x27x64, 3x3 / pad 1 on 13x13 x 192 / 384 /
+// 256; CO % 32 == 0. x bf16 NHWC, wf: fragment-order weights (stream_frag_index,
+// K = ks ks CI), y = relu?(conv + bias) [B, H, W, CO]. pool (the 5x5 and the
+// 256-channel 3x3, with ReLU only): y = the 3x3/s2 max-pool of the bf16-rounded
+// output instead, [B, (H-3)/2+1, (W-3)/2+1, CO]; the un-pooled output is not
+// written and mf is not read. mf: pixel fragments of 16 per workgroup (1, 2 or
+// 4; conv_smallk_pick_mf).
+bool conv_smallk_supported(int H, int W, int CI, int CO, int ks, int pad, bool pool);
+int conv_smallk_pick_mf(int B, int H, int W, int CI, int CO, int ks, int num_cus);
+void conv_smallk(const void* x, const void* wf, const float* bias, void* y, int B, int H, int W, int CI, int CO, int ks,
+                 int pad, bool relu, bool pool, int mf, hipStream_t s);
 // Direct 3x3/p1 conv with the input image resident in LDS and per-wave weight
 // rings (conv3x3_stream.hip): stride 1 on 28x28x128, 14x14x256, 7x7x512;
 // stride 2 on 56x56x64 -> 128 and 28x28x128 -> 256. Hin/Win are the input
@@ -457,6 +469,9 @@ bool alex_stem_supported(int S);
 int alex_stem_k(int kh, int kw, int c);
 constexpr int kAlexStemK = 544;
 void alex_stem_u8(const uint8_t* x, const void* w, const float* bias, void* y, int B, hipStream_t s);
+// The same operands and, bit for bit, the same result at query batches
+// (alex_stem_rows.hip): one workgroup per pooled output row instead of one per image.
+void alex_stem_rows_u8(const uint8_t* x, const void* w, const float* bias, void* y, int B, hipStream_t s);
 
 // One wave of v_mfma_scale_f32_16x16x128_f8f6f4 (fp8 e4m3, unit scales) on
 // raw per-lane registers: a, b = int32 [64 lanes][8], d = f32 [64 lanes][4].

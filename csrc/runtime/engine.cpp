@@ -43,6 +43,7 @@ bool EngineOptions::set(const std::string& name, bool v) {
       {"igemm_small_m", &EngineOptions::igemm_small_m},
       {"small_conv", &EngineOptions::small_conv},
       {"small_conv8", &EngineOptions::small_conv8},
+      {"small_alex", &EngineOptions::small_alex},
   };
   for (const auto& f : fields)
     if (name == f.first) {
@@ -582,7 +583,7 @@ void Engine::run_ops(const std::vector<Step>& steps, const Request& req, hipStre
   // the u8 kernels and PackTensor each read their own kind of input: a plan
   // made for the other kind is refused before anything is launched
   for (const Step& st : steps) {
-    const bool u8 = st.kernel == Kernel::AlexStem || st.kernel == Kernel::Preprocess || st.kernel == Kernel::StemPoolU8;
+    const bool u8 = st.kernel == Kernel::AlexStem || st.kernel == Kernel::AlexStemRows || st.kernel == Kernel::Preprocess || st.kernel == Kernel::StemPoolU8;
     if ((u8 && in.tensor) || (st.kernel == Kernel::PackTensor && !in.tensor))
       throw std::logic_error(std::string("plan step ") + kernel_name(st.kernel) + " does not read this input");
     if (st.kernel == Kernel::Embed && !features) throw std::logic_error("plan step Embed without a features buffer");
@@ -629,9 +630,11 @@ void Engine::run_ops(const std::vector<Step>& steps, const Request& req, hipStre
     switch (st.kernel) {
       case Kernel::None:
         break;
-      case Kernel::AlexStem: {
+      case Kernel::AlexStem:
+      case Kernel::AlexStemRows: {
         const ConvLayer& L = convs_[ops_[oi + 1].conv];
-        alex_stem_u8(images, W(L.wf_off), F(L.b_off), acts_[ops_[oi + 2].out], B, s);
+        (st.kernel == Kernel::AlexStem ? alex_stem_u8 : alex_stem_rows_u8)(images, W(L.wf_off), F(L.b_off),
+                                                                            acts_[ops_[oi + 2].out], B, s);
         break;
       }
       case Kernel::Preprocess: {
@@ -745,6 +748,10 @@ void Engine::run_ops(const std::vector<Step>& steps, const Request& req, hipStre
         conv_small(acts_[op.in], W(Lp->wf_off), F(Lp->b_off), res, acts_[op.out], B, isp->H, isp->W, isp->C, Lp->cout,
                    Lp->stride, Lp->relu, st.count, cs, D ? W(D->wf_off) : nullptr, D ? F(D->b_off) : nullptr,
                    D ? acts_[d->out] : nullptr);
+        break;
+      case Kernel::SmallK:  // with ypool the un-pooled activation is never written
+        conv_smallk(acts_[op.in], W(Lp->wf_off), F(Lp->b_off), ypool ? ypool : acts_[op.out], B, isp->H, isp->W, isp->C,
+                    Lp->cout, Lp->kh, Lp->pad, Lp->relu, ypool != nullptr, st.count, cs);
         break;
       case Kernel::Small8:
       case Kernel::Stream8: {

@@ -103,6 +103,15 @@ constexpr int kSmallConv8MaxB = 32;
 // A/B hook (tools/small8_bench.py times larger batches on the e4m3 query-batch
 // path): the bound the planner uses, 0 = kSmallConv8MaxB
 void small_conv8_set_max_b(int b);
+// ... on AlexNet's query-batch kernels (small_alex: alex_stem_rows.hip, conv_smallk.hip): the largest power of
+// two at which the forward with the option on is faster than with it off, interleaved graph replays
+// (profiles/alex_small.txt; one bound for both kernels: the sweep gives no reason for two):
+//   B            1      2      4      8      16     32     64
+//   off   us   310.2  315.2  317.9  321.3  328.0  340.6  345.6
+//   on    us    80.1   85.3   95.8  125.9  178.9  287.6  473.7     (two "off" engines differ by <= 2.0 us)
+// A/B hook (tools/alex_small_bench.py): the bound the planner uses, 0 = kSmallAlexMaxB
+constexpr int kSmallAlexMaxB = 32;
+void small_alex_set_max_b(int b);
 constexpr int kPoolThenHeadB = 32;  // from this batch on an unfused-pool head pools once, then head_pooled
 
 struct EngineOptions {
@@ -119,6 +128,10 @@ struct EngineOptions {
   // kSmallConv8MaxB, conv_small8.hip) instead of the e4m3 implicit GEMM; off
   // until the default plans are re-recorded with profiles/small8.txt in hand
   bool small_conv8 = false;
+  // alexnet / alexnet_fp8 at B <= kSmallAlexMaxB: the fused u8 stem on alex_stem_rows.hip (one workgroup per
+  // pooled row) and features.3 / .6 / .8 / .10 (+ the pools after .3 and .10) as one conv_smallk.hip launch
+  // each, spread over the CUs, instead of one workgroup per image on alex_stem.hip / conv_direct.hip; off until the default plans are re-recorded with profiles/alex_small.txt in hand
+  bool small_alex = false;
   bool fused_stem = true;       // conv1 + BN + ReLU + maxpool in one kernel (stem_pool.hip)
   bool fused_preprocess = true;  // SxS u8 images straight into the fused stem (no preprocess pass)
   bool row_conv = true;          // direct row-streaming 3x3 convs (conv3x3_rows.hip) for 56x56x64
@@ -219,7 +232,7 @@ enum class Kernel {
   AlexStem, StemPoolU8, StemPool, FcSmall, Conv1x1Cat, Conv1x1Chain, Bottleneck56, Bottleneck56Head, Block,
   S2Rows, S2Rows128, Stream, Stream8, Rows28, Rows, Small, Direct13, Direct27, Conv1x1, BigTile, Igemm, FcGemm,
   HeadPooled, HeadFused, AvgPoolGlobal, AvgPoolAdaptive, MaxPool, Preprocess, PackTensor, SoftmaxTop1, SoftmaxTopK,
-  Embed, QuantE4m3, FcSmall8, FcGemm8, Small8
+  Embed, QuantE4m3, FcSmall8, FcGemm8, Small8, SmallK, AlexStemRows
 };
 const char* kernel_name(Kernel k);
 
@@ -230,12 +243,12 @@ struct Step {
   // (S2Rows, Stream, Stream8, Small, Small8), or as extra K steps with no activation written
   // (Rows28: ds_into_conv2, Conv1x1Cat: ds_into_expand)
   int ds_op = -1;
-  int pool_op = -1;      // pool op whose output the conv's epilogue writes (Stream, Direct13, Direct27)
+  int pool_op = -1;      // pool op whose output the conv's epilogue writes (Stream, Direct13, Direct27, SmallK)
   bool wreg = false;     // weights from the layer's FragOrder copy (Stream, Rows: register-streamed; StemPoolU8: dense K)
   bool store_y = true;   // false: the last op's activation is not written (Stream with the pool fused, under a graph)
   bool side = false;     // runs on the side stream (fork_ds)
   int cfg = -1;          // BigTile: tile config
-  // Rows / StemPool / StemPoolU8: strip; Small / Small8: mf; BigTile / FcGemm / FcGemm8: K splits; SoftmaxTopK: k;
+  // Rows / StemPool / StemPoolU8: strip; Small / Small8 / SmallK: mf; BigTile / FcGemm / FcGemm8: K splits; SoftmaxTopK: k;
   // Embed: the pixels it averages (0: src_op's output is the feature row itself)
   int count = 0;
   int src_op = -1;       // Embed: the op whose output activation it reads

@@ -82,15 +82,17 @@ const char* kernel_name(Kernel k) {
       "Bottleneck56Head", "Block", "S2Rows", "S2Rows128", "Stream", "Stream8", "Rows28", "Rows", "Small", "Direct13",
       "Direct27", "Conv1x1", "BigTile", "Igemm", "FcGemm", "HeadPooled", "HeadFused", "AvgPoolGlobal",
       "AvgPoolAdaptive", "MaxPool", "Preprocess", "PackTensor", "SoftmaxTop1", "SoftmaxTopK", "Embed", "QuantE4m3",
-      "FcSmall8", "FcGemm8", "Small8"};
-  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::Small8 + 1, "one name per Kernel");
+      "FcSmall8", "FcGemm8", "Small8", "SmallK", "AlexStemRows"};
+  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::AlexStemRows + 1, "one name per Kernel");
   return names[(size_t)k];
 }
 
 namespace {
 int g_small_conv8_max_b = 0;  // small_conv8_set_max_b
+int g_small_alex_max_b = 0;   // small_alex_set_max_b
 }
 void small_conv8_set_max_b(int b) { g_small_conv8_max_b = b; }
+void small_alex_set_max_b(int b) { g_small_alex_max_b = b; }
 
 // ---------------------------------------------------------------- planner
 // What to launch for one forward of B images: each conv op's kernel path
@@ -98,7 +100,7 @@ void small_conv8_set_max_b(int b) { g_small_conv8_max_b = b; }
 // launch swallows. Reads the graph, the layout pass's results (frag, cat_off,
 // npad) and num_cus_; no device state.
 struct Engine::Planner {
-  enum class Path { Stream, Rows, Rows28, Direct13, Direct27, OneByOne, BigTile, Igemm, Small, Stream8, Small8, Fc };
+  enum class Path { Stream, Rows, Rows28, Direct13, Direct27, OneByOne, BigTile, Igemm, Small, Stream8, Small8, Fc, SmallK };
 
   const Engine& e;
   const std::vector<Op>& ops;
@@ -136,6 +138,12 @@ struct Engine::Planner {
   // one-workgroup-per-image kernels: only with rounds of num_cus images that are >= ~70% full
   bool full_rounds() const { return 10 * B >= 7 * ((B + cus - 1) / cus) * cus; }
 
+  // AlexNet on its query-batch kernels (conv_smallk.hip, alex_stem_rows.hip)
+  bool small_alex() const {
+    return opt.small_alex && (e.arch_ == "alexnet" || e.arch_ == "alexnet_fp8") &&
+           B <= (g_small_alex_max_b > 0 ? g_small_alex_max_b : kSmallAlexMaxB);
+  }
+
   Path conv_path(const Op& op) const {
     const ConvLayer& L = convs[op.conv];
     const ActShape& is = shapes[op.in];
@@ -151,6 +159,11 @@ struct Engine::Planner {
     // register weights 48.1 vs 13.2 + 46.3 us (profiles/r1_fused_ds.txt)
     const bool l4s2 = L.stride == 2 && is.H < 28 && !(opt.stream_l4s2 && opt.stream_wreg);
     const bool l1 = L.stride == 1 && is.C == 64;  // layer1: conv3x3_rows (the stream conv measured slower there)
+    // AlexNet at query batches: its four stride-1 feature convs spread over the CUs (conv_smallk.hip)
+    if (small_alex() && L.plain() && L.stride == 1 &&
+        L.kh == L.kw && L.frag == FragOrder::Stream && L.kpad == L.kh * L.kw * is.C && !shapes[op.out].f32 &&
+        !shapes[op.out].fp8 && conv_smallk_supported(is.H, is.W, is.C, L.cout, L.kh, L.pad, false))
+      return Path::SmallK;
     // query batches: one launch per conv, no split-K (conv_small.hip)
     if (opt.small_conv && k3 && L.frag == FragOrder::Stream && B <= kSmallConvMaxB &&
         conv_small_supported(is.H, is.W, is.C, L.cout, L.stride) &&
@@ -498,6 +511,18 @@ struct Engine::Planner {
           st.n_ops = 2;
         }
         break;
+      case Path::SmallK: {  // features.3 + features.5, features.10 + features.12 as Direct27 / Direct13 take them
+        st.kernel = Kernel::SmallK;
+        const int po = (is.H - 3) / 2 + 1;
+        if (!side && L.relu && conv_smallk_supported(is.H, is.W, is.C, L.cout, L.kh, L.pad, true) &&
+            maxpool_fusable(oi, po)) {
+          st.pool_op = (int)oi + 1;
+          st.n_ops = 2;
+        } else {
+          st.count = conv_smallk_pick_mf(B, is.H, is.W, is.C, L.cout, L.kh, cus);
+        }
+        break;
+      }
       case Path::Small:
         st.kernel = Kernel::Small;
         st.ds_op = ds;
@@ -616,7 +641,7 @@ struct Engine::Planner {
           // AlexNet: 224x224 u8 images -> features.2's output in one kernel
           if (native && opt.fused_preprocess && conv(oi + 1) && oi + 2 < ops.size() &&
               ops[oi + 2].type == OpType::MaxPool && convs[ops[oi + 1].conv].alex_stem)
-            emit(Kernel::AlexStem, oi, 3);
+            emit(small_alex() ? Kernel::AlexStemRows : Kernel::AlexStem, oi, 3);
           // images already SxS feed the fused stem directly (StemPoolU8)
           else if (native && opt.fused_preprocess && op.k == 1)
             emit(Kernel::None, oi, 1);
@@ -718,7 +743,7 @@ std::string Engine::step_detail(const Step& st) const {
   if (st.side) add("side");
   if (st.cfg >= 0) add("cfg=" + std::to_string(st.cfg));
   if (st.count > 0) {
-    const char* what = (st.kernel == Kernel::Small || st.kernel == Kernel::Small8) ? "mf=" : st.kernel == Kernel::SoftmaxTopK ? "k=" : st.kernel == Kernel::Embed ? "hw=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm || st.kernel == Kernel::FcGemm8) ? "splits=" : "strip=";
+    const char* what = (st.kernel == Kernel::Small || st.kernel == Kernel::Small8 || st.kernel == Kernel::SmallK) ? "mf=" : st.kernel == Kernel::SoftmaxTopK ? "k=" : st.kernel == Kernel::Embed ? "hw=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm || st.kernel == Kernel::FcGemm8) ? "splits=" : "strip=";
     add(what + std::to_string(st.count));
   }
   return d;

@@ -313,6 +313,40 @@ def conv_small(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, res:
     return (y, yd) if wd_packed is not None else y
 
 
+def conv_smallk(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, ks: int, pad: int, relu: bool = True,
+                pool: bool = False, mf: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Query-batch k x k / s1 conv of AlexNet's feature convs (conv_smallk.hip)
+    on NHWC bf16: relu?(conv(x) + bias) for 5x5 / pad 2 on [B,27,27,64] and 3x3 /
+    pad 1 on [B,13,13,192 | 384 | 256]. w_packed: conv2d packed weights [Cout,
+    ks ks CI]. pool (the 5x5 and the 256-channel 3x3, ReLU only): the following
+    3x3/s2 max-pool taken in LDS, [B,13,13,Cout] / [B,6,6,Cout] returned instead.
+    mf: pixel fragments of 16 per workgroup (1, 2, 4; None: conv_smallk_pick_mf;
+    not read with pool). out: the output tensor to write."""
+    _need_cuda(x, w_packed, bias, out)
+    C = native()
+    if x.dim() != 4 or x.dtype != torch.bfloat16 or w_packed.dtype != torch.bfloat16:
+        raise ValueError("conv_smallk: x is bf16 NHWC, w_packed bf16 [Cout, ks ks CI]")
+    B, H, W, Cin = x.shape
+    Cout = w_packed.shape[0]
+    if not C.conv_smallk_supported(H, W, Cin, Cout, ks, pad, pool) or tuple(w_packed.shape) != (Cout, ks * ks * Cin) \
+            or bias.numel() != Cout:
+        raise ValueError("conv_smallk: unsupported shape")
+    if pool and not relu:
+        raise ValueError("conv_smallk: the fused max-pool needs ReLU")
+    if mf is None:
+        cus = torch.cuda.get_device_properties(x.device).multi_processor_count
+        mf = C.conv_smallk_pick_mf(B, H, W, Cin, Cout, ks, cus)
+    Ho = (H - 3) // 2 + 1 if pool else H
+    if out is None:
+        out = torch.empty(B, Ho, Ho, Cout, dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (B, Ho, Ho, Cout) or out.dtype != x.dtype or not out.is_contiguous():
+        raise ValueError("conv_smallk: out has the output's shape, bf16, contiguous")
+    bias = bias if bias.dtype == torch.float32 and bias.is_contiguous() else bias.float().contiguous()
+    C.conv_smallk(_ptr(x.contiguous()), _ptr(stream_weight_frag(w_packed)), _ptr(bias), _ptr(out), B, H, W, Cin, Cout,
+                  ks, pad, relu, pool, mf, _stream())
+    return out
+
+
 def conv3x3_rows28(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, res: torch.Tensor | None = None,
                    relu: bool = True, downsample: tuple | None = None, out_inv_scale: float = 0.0) -> torch.Tensor:
     """Weight-stationary row-streaming 3x3/s1/p1 conv on [B,28,28,128] ->
@@ -939,7 +973,7 @@ def pack_alex_stem_weight(w: torch.Tensor, scale: torch.Tensor | None = None, de
     return out.to(device) if device is not None else out
 
 
-def alex_stem(images: torch.Tensor, w: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+def alex_stem(images: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, _launch: str = "alex_stem_u8") -> torch.Tensor:
     """AlexNet features.0-2 in one kernel (alex_stem.hip): u8 [B, 224, 224, 3]
     -> ImageNet normalisation (``preprocess_u8``'s values) -> conv 11x11/s4/p2 +
     bias -> ReLU -> maxpool 3x3/s2 -> bf16 [B, 27, 27, 64]. w:
@@ -955,8 +989,15 @@ def alex_stem(images: torch.Tensor, w: torch.Tensor, bias: torch.Tensor) -> torc
         raise ValueError("alex_stem: bias holds 64 values")
     B = images.shape[0]
     y = torch.empty(B, 27, 27, 64, device=images.device, dtype=torch.bfloat16)
-    C.alex_stem_u8(_ptr(images.contiguous()), _ptr(w), _ptr(bias.float().contiguous()), _ptr(y), B, _stream())
+    getattr(C, _launch)(_ptr(images.contiguous()), _ptr(w), _ptr(bias.float().contiguous()), _ptr(y), B, _stream())
     return y
+
+
+def alex_stem_rows(images: torch.Tensor, w: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """``alex_stem`` at query batches (alex_stem_rows.hip): the same operands and,
+    bit for bit, the same result, one workgroup per pooled output row instead of
+    one per image."""
+    return alex_stem(images, w, bias, _launch="alex_stem_rows_u8")
 
 
 def conv5x5_27(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, pool: bool = False) -> torch.Tensor:

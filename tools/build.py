@@ -119,6 +119,7 @@ HIPCC_FILE_FLAGS = {
     "conv3x3_stream8_block.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "fc8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "conv_small8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "conv_smallk.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 
