@@ -142,6 +142,34 @@ ConvArgs chain_conv(uintptr_t x, uintptr_t w, uintptr_t alpha, uintptr_t bias, u
   return a;
 }
 
+// a 1x1 conv's ConvArgs for the conv1x1_small bindings (pointers may be 0 for the geometry-only entries)
+ConvArgs small1x1_conv(uintptr_t x, uintptr_t w, uintptr_t alpha, uintptr_t bias, uintptr_t res, uintptr_t y, int B, int H,
+                       int W, int Cin, int N, int Kpad, int stride, bool relu, bool in_fp8, bool out_fp8, float res_scale,
+                       float out_inv_scale) {
+  ConvArgs a;
+  a.x = P<void>(x);
+  a.w = P<void>(w);
+  a.alpha = P<float>(alpha);
+  a.bias = P<float>(bias);
+  a.res = P<void>(res);
+  a.y = P<void>(y);
+  a.B = B;
+  a.H = H;
+  a.W = W;
+  a.Ho = conv_out_dim(H, 1, stride, 0);
+  a.Wo = conv_out_dim(W, 1, stride, 0);
+  a.Cin = Cin;
+  a.Kpad = Kpad;
+  a.N = a.Npad = a.ldo = N;
+  a.stride = stride;
+  a.relu = relu;
+  a.in_fp8 = in_fp8;
+  a.out_fp8 = out_fp8;
+  a.res_scale = res_scale;
+  a.out_inv_scale = out_inv_scale;
+  return a;
+}
+
 const JpegGpuImage* host_descs(const py::array_t<uint8_t, py::array::c_style>& a, int* n) {
   if (a.size() % (py::ssize_t)sizeof(JpegGpuImage)) throw std::invalid_argument("jpeg descriptors: bad size");
   *n = (int)(a.size() / (py::ssize_t)sizeof(JpegGpuImage));
@@ -564,6 +592,27 @@ PYBIND11_MODULE(_C, m) {
         py::arg("CI"), py::arg("CO"), py::arg("ks"), py::arg("pad"), py::arg("relu"), py::arg("pool"), py::arg("mf"),
         py::arg("stream"));
   m.def("small_alex_set_max_b", &small_alex_set_max_b);
+  m.def("conv1x1_small_supported", [](int B, int H, int W, int Cin, int N, int stride, bool in_fp8, bool out_fp8) {
+    return conv1x1_small_supported(small1x1_conv(0, 0, 0, 0, 0, 0, B, H, W, Cin, N, Cin, stride, true, in_fp8, out_fp8, 1.f, 1.f));
+  }, py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("N"), py::arg("stride"), py::arg("in_fp8"),
+        py::arg("out_fp8"));
+  m.def("conv1x1_small_pick", [](int B, int H, int W, int Cin, int N, int stride, bool in_fp8, bool out_fp8, int num_cus) {
+    return conv1x1_small_pick(small1x1_conv(0, 0, 0, 0, 0, 0, B, H, W, Cin, N, Cin, stride, true, in_fp8, out_fp8, 1.f, 1.f),
+                              num_cus);
+  }, py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("N"), py::arg("stride"), py::arg("in_fp8"),
+        py::arg("out_fp8"), py::arg("num_cus"));
+  m.attr("kSmall1x1MaxB") = kSmall1x1MaxB;
+  m.def("small_1x1_set_max_b", &small_1x1_set_max_b);
+  m.def("conv1x1_small", [](uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, int B, int H, int W, int Cin, int N,
+                            int stride, bool relu, bool in_fp8, bool out_fp8, int mf, int nf, uintptr_t stream,
+                            uintptr_t alpha, uintptr_t res, float res_scale, float out_inv_scale, int Kpad) {
+    conv1x1_small(small1x1_conv(x, w, alpha, bias, res, y, B, H, W, Cin, N, Kpad > 0 ? Kpad : Cin, stride, relu, in_fp8,
+                                out_fp8, res_scale, out_inv_scale),
+                  mf, nf, S(stream));
+  }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("B"), py::arg("H"), py::arg("W"),
+        py::arg("Cin"), py::arg("N"), py::arg("stride"), py::arg("relu"), py::arg("in_fp8"), py::arg("out_fp8"),
+        py::arg("mf"), py::arg("nf"), py::arg("stream") = 0, py::arg("alpha") = 0, py::arg("res") = 0,
+        py::arg("res_scale") = 1.f, py::arg("out_inv_scale") = 1.f, py::arg("Kpad") = 0);
   m.attr("kSmallAlexMaxB") = kSmallAlexMaxB;
   m.def("conv3x3_rows28_supported", &conv3x3_rows28_supported);
   m.def("conv3x3_rows28", [](uintptr_t x, uintptr_t wf, uintptr_t bias, uintptr_t res, uintptr_t y, int B, bool relu,

@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include <stdexcept>
 #include <string>
+#include <utility>
 
 namespace dmlc {
 
@@ -121,6 +122,18 @@ struct C1Plan {
 };
 C1Plan conv1x1_plan(bool in8, bool out8, int rb, int nw, bool res, int s, int wv, bool ch);
 void conv1x1_chain(const ConvArgs& a, const ConvArgs& r, int num_cus, hipStream_t s);
+// Query-batch 1x1 conv (conv1x1_small.hip): conv1x1's operands (the layer's
+// row-major [Npad][Kpad] weights, alpha / bias, a residual of the output's
+// dtype, the ConvArgs fp8 fields; in and out types independent), stride 1 or
+// 2, no padding, any M = B*Ho*Wo. Cin in {64, 128, 256, .., 2048} (bf16) or
+// {128, 256, .., 2048} (e4m3), N % 16 == 0, ldo == N; no x2 / split_k / out_f32.
+// A workgroup owns nf 16-channel x mf 16-pixel fragments: (mf, nf) in {(1,1),
+// (2,1), (4,1), (4,2), (8,2), (8,4)}, nf dividing N / 16, bounded by the K
+// steps a wave keeps in registers (conv1x1_small_pick returns a valid pair).
+// y / res: 8-B (bf16) or 4-B (e4m3) aligned; x and w 16-B.
+bool conv1x1_small_supported(const ConvArgs& a);                      // geometry only: no pointer is read
+std::pair<int, int> conv1x1_small_pick(const ConvArgs& a, int num_cus);  // (mf, nf)
+void conv1x1_small(const ConvArgs& a, int mf, int nf, hipStream_t s);
 int conv_bigtile_pick(const ConvArgs& a, int num_cus);  // engine's choice: config, or -1 (old kernel)
 int conv_bigtile_splits(const ConvArgs& a, int cfg, int num_cus);
 long conv_bigtile_slabs(const ConvArgs& a, int cfg, int splits);

@@ -43,6 +43,7 @@ bool EngineOptions::set(const std::string& name, bool v) {
       {"igemm_small_m", &EngineOptions::igemm_small_m},
       {"small_conv", &EngineOptions::small_conv},
       {"small_conv8", &EngineOptions::small_conv8},
+      {"small_1x1", &EngineOptions::small_1x1},
       {"small_alex", &EngineOptions::small_alex},
   };
   for (const auto& f : fields)
@@ -792,6 +793,13 @@ void Engine::run_ops(const std::vector<Step>& steps, const Request& req, hipStre
         bind(a, op, logits);
         a.split_k = 1;
         conv1x1(a, num_cus_, cs);
+        break;
+      }
+      case Kernel::Small1x1: {  // st.count = mf, st.cfg = nf
+        ConvArgs a = conv_geom(op, B);
+        bind(a, op, logits);
+        a.split_k = 1;
+        conv1x1_small(a, st.count, st.cfg, cs);
         break;
       }
       case Kernel::BigTile: {

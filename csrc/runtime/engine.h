@@ -103,6 +103,11 @@ constexpr int kSmallConv8MaxB = 32;
 // A/B hook (tools/small8_bench.py times larger batches on the e4m3 query-batch
 // path): the bound the planner uses, 0 = kSmallConv8MaxB
 void small_conv8_set_max_b(int b);
+// ... and the query-batch 1x1 conv path (small_1x1, conv1x1_small.hip): faster than the default plan
+// for resnet50 up to B = 8 (slower at 16) and for resnet50_fp8 up to 16 (slower at 32), so 8 for both
+// (profiles/small1x1.txt); the same A/B hook (tools/small1x1_bench.py)
+constexpr int kSmall1x1MaxB = 8;
+void small_1x1_set_max_b(int b);
 // ... on AlexNet's query-batch kernels (small_alex: alex_stem_rows.hip, conv_smallk.hip): the largest power of
 // two at which the forward with the option on is faster than with it off, interleaved graph replays
 // (profiles/alex_small.txt; one bound for both kernels: the sweep gives no reason for two):
@@ -128,6 +133,10 @@ struct EngineOptions {
   // kSmallConv8MaxB, conv_small8.hip) instead of the e4m3 implicit GEMM; off
   // until the default plans are re-recorded with profiles/small8.txt in hand
   bool small_conv8 = false;
+  // ResNet50's 1x1 convs at query batches (B <= kSmall1x1MaxB) on conv1x1_small.hip instead of
+  // the implicit GEMM / conv1x1 / the one-workgroup-per-image layer1 bottleneck kernels
+  // (whose members then run unfused); off like small_conv8
+  bool small_1x1 = false;
   // alexnet / alexnet_fp8 at B <= kSmallAlexMaxB: the fused u8 stem on alex_stem_rows.hip (one workgroup per
   // pooled row) and features.3 / .6 / .8 / .10 (+ the pools after .3 and .10) as one conv_smallk.hip launch
   // each, spread over the CUs, instead of one workgroup per image on alex_stem.hip / conv_direct.hip; off until the default plans are re-recorded with profiles/alex_small.txt in hand
@@ -232,7 +241,7 @@ enum class Kernel {
   AlexStem, StemPoolU8, StemPool, FcSmall, Conv1x1Cat, Conv1x1Chain, Bottleneck56, Bottleneck56Head, Block,
   S2Rows, S2Rows128, Stream, Stream8, Rows28, Rows, Small, Direct13, Direct27, Conv1x1, BigTile, Igemm, FcGemm,
   HeadPooled, HeadFused, AvgPoolGlobal, AvgPoolAdaptive, MaxPool, Preprocess, PackTensor, SoftmaxTop1, SoftmaxTopK,
-  Embed, QuantE4m3, FcSmall8, FcGemm8, Small8, SmallK, AlexStemRows
+  Embed, QuantE4m3, FcSmall8, FcGemm8, Small8, SmallK, AlexStemRows, Small1x1
 };
 const char* kernel_name(Kernel k);
 
@@ -247,8 +256,8 @@ struct Step {
   bool wreg = false;     // weights from the layer's FragOrder copy (Stream, Rows: register-streamed; StemPoolU8: dense K)
   bool store_y = true;   // false: the last op's activation is not written (Stream with the pool fused, under a graph)
   bool side = false;     // runs on the side stream (fork_ds)
-  int cfg = -1;          // BigTile: tile config
-  // Rows / StemPool / StemPoolU8: strip; Small / Small8 / SmallK: mf; BigTile / FcGemm / FcGemm8: K splits; SoftmaxTopK: k;
+  int cfg = -1;          // BigTile: tile config; Small1x1: nf
+  // Rows / StemPool / StemPoolU8: strip; Small / Small8 / SmallK / Small1x1: mf; BigTile / FcGemm / FcGemm8: K splits; SoftmaxTopK: k;
   // Embed: the pixels it averages (0: src_op's output is the feature row itself)
   int count = 0;
   int src_op = -1;       // Embed: the op whose output activation it reads

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <stdexcept>
+#include <tuple>
 
 namespace dmlc {
 
@@ -82,17 +83,19 @@ const char* kernel_name(Kernel k) {
       "Bottleneck56Head", "Block", "S2Rows", "S2Rows128", "Stream", "Stream8", "Rows28", "Rows", "Small", "Direct13",
       "Direct27", "Conv1x1", "BigTile", "Igemm", "FcGemm", "HeadPooled", "HeadFused", "AvgPoolGlobal",
       "AvgPoolAdaptive", "MaxPool", "Preprocess", "PackTensor", "SoftmaxTop1", "SoftmaxTopK", "Embed", "QuantE4m3",
-      "FcSmall8", "FcGemm8", "Small8", "SmallK", "AlexStemRows"};
-  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::AlexStemRows + 1, "one name per Kernel");
+      "FcSmall8", "FcGemm8", "Small8", "SmallK", "AlexStemRows", "Small1x1"};
+  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)Kernel::Small1x1 + 1, "one name per Kernel");
   return names[(size_t)k];
 }
 
 namespace {
 int g_small_conv8_max_b = 0;  // small_conv8_set_max_b
 int g_small_alex_max_b = 0;   // small_alex_set_max_b
+int g_small_1x1_max_b = 0;    // small_1x1_set_max_b
 }
 void small_conv8_set_max_b(int b) { g_small_conv8_max_b = b; }
 void small_alex_set_max_b(int b) { g_small_alex_max_b = b; }
+void small_1x1_set_max_b(int b) { g_small_1x1_max_b = b; }
 
 // ---------------------------------------------------------------- planner
 // What to launch for one forward of B images: each conv op's kernel path
@@ -100,7 +103,7 @@ void small_alex_set_max_b(int b) { g_small_alex_max_b = b; }
 // launch swallows. Reads the graph, the layout pass's results (frag, cat_off,
 // npad) and num_cus_; no device state.
 struct Engine::Planner {
-  enum class Path { Stream, Rows, Rows28, Direct13, Direct27, OneByOne, BigTile, Igemm, Small, Stream8, Small8, Fc, SmallK };
+  enum class Path { Stream, Rows, Rows28, Direct13, Direct27, OneByOne, BigTile, Igemm, Small, Stream8, Small8, Fc, SmallK, Small1x1 };
 
   const Engine& e;
   const std::vector<Op>& ops;
@@ -142,6 +145,12 @@ struct Engine::Planner {
   bool small_alex() const {
     return opt.small_alex && (e.arch_ == "alexnet" || e.arch_ == "alexnet_fp8") &&
            B <= (g_small_alex_max_b > 0 ? g_small_alex_max_b : kSmallAlexMaxB);
+  }
+
+  // ResNet50 on its query-batch 1x1 conv kernel (conv1x1_small.hip)
+  bool small_1x1() const {
+    return opt.small_1x1 && (e.arch_ == "resnet50" || e.arch_ == "resnet50_fp8") &&
+           B <= (g_small_1x1_max_b > 0 ? g_small_1x1_max_b : kSmall1x1MaxB);
   }
 
   Path conv_path(const Op& op) const {
@@ -203,6 +212,15 @@ struct Engine::Planner {
         conv3x3_stream_supported(is.H, is.W, is.C, L.cout, L.stride))
       return Path::Stream;
     if (opt.row_conv && k3 && L.stride == 1 && conv3x3_rows_supported(is.H, is.W, is.C, L.cout)) return Path::Rows;
+    // 1x1 convs at query batches: one launch, every load up front (conv1x1_small.hip); the residual is
+    // of the output's type
+    if (small_1x1() && !L.fc && L.kh == 1 && L.kw == 1 && !shapes[op.out].f32 &&
+        (op.res < 0 || (!shapes[op.res].f32 && shapes[op.res].fp8 == shapes[op.out].fp8 &&
+                        shapes[op.res].cscale.empty()))) {
+      ConvArgs a = e.conv_geom(op, B);
+      a.split_k = 1;
+      if (conv1x1_small_supported(a)) return Path::Small1x1;
+    }
     if (opt.conv1x1 && !L.fc && L.kh == 1 && L.kw == 1) {
       ConvArgs a = e.conv_geom(op, B);
       a.split_k = 1;
@@ -320,7 +338,7 @@ struct Engine::Planner {
   // conv3 (1x1 64 -> 256 + the block input as residual, e4m3 out) of a
   // resnet50_fp8 layer1 identity block, the intermediates read by nothing else.
   bool bottleneck_fusable(size_t oi) const {
-    if (!opt.fused_bottleneck || !e.fp8_ || !conv(oi + 1) || !conv(oi + 2)) return false;
+    if (!opt.fused_bottleneck || small_1x1() || !e.fp8_ || !conv(oi + 1) || !conv(oi + 2)) return false;
     const Op& c1 = ops[oi];
     const Op& c2 = ops[oi + 1];
     const Op& c3 = ops[oi + 2];
@@ -341,7 +359,7 @@ struct Engine::Planner {
 
   // ops[oi], ops[oi+1] = layer1.0's reduce 1x1 (64 -> 64) + 3x3 -> bottleneck56_head
   bool bottleneck_head_fusable(size_t oi) const {
-    if (!opt.fused_bottleneck || !conv(oi + 1)) return false;
+    if (!opt.fused_bottleneck || small_1x1() || !conv(oi + 1)) return false;
     const Op& c1 = ops[oi];
     const Op& c2 = ops[oi + 1];
     if (c1.side || c2.side || c2.in != c1.out || c1.res >= 0 || c2.res >= 0) return false;
@@ -552,6 +570,13 @@ struct Engine::Planner {
       case Path::OneByOne:
         st.kernel = Kernel::Conv1x1;
         break;
+      case Path::Small1x1: {
+        ConvArgs a = e.conv_geom(op, B);
+        a.split_k = 1;
+        st.kernel = Kernel::Small1x1;
+        std::tie(st.count, st.cfg) = conv1x1_small_pick(a, cus);  // (mf, nf)
+        break;
+      }
       case Path::BigTile: {
         const ConvArgs a = e.conv_geom(op, B);
         st.kernel = Kernel::BigTile;
@@ -741,9 +766,9 @@ std::string Engine::step_detail(const Step& st) const {
   if (st.wreg) add("wreg");
   if (!st.store_y) add("nostore");
   if (st.side) add("side");
-  if (st.cfg >= 0) add("cfg=" + std::to_string(st.cfg));
+  if (st.cfg >= 0) add((st.kernel == Kernel::Small1x1 ? "nf=" : "cfg=") + std::to_string(st.cfg));
   if (st.count > 0) {
-    const char* what = (st.kernel == Kernel::Small || st.kernel == Kernel::Small8 || st.kernel == Kernel::SmallK) ? "mf=" : st.kernel == Kernel::SoftmaxTopK ? "k=" : st.kernel == Kernel::Embed ? "hw=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm || st.kernel == Kernel::FcGemm8) ? "splits=" : "strip=";
+    const char* what = (st.kernel == Kernel::Small || st.kernel == Kernel::Small8 || st.kernel == Kernel::SmallK || st.kernel == Kernel::Small1x1) ? "mf=" : st.kernel == Kernel::SoftmaxTopK ? "k=" : st.kernel == Kernel::Embed ? "hw=" : (st.kernel == Kernel::BigTile || st.kernel == Kernel::FcGemm || st.kernel == Kernel::FcGemm8) ? "splits=" : "strip=";
     add(what + std::to_string(st.count));
   }
   return d;

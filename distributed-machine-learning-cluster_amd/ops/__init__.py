@@ -752,6 +752,50 @@ def conv_small8(x: torch.Tensor, w_q: torch.Tensor, alpha: torch.Tensor, bias: t
     return y if wd is None else (y, yd)
 
 
+def conv1x1_small(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, alpha: torch.Tensor | None = None,
+                  res: torch.Tensor | None = None, res_scale: float = 1.0, stride: int = 1, relu: bool = True,
+                  out_scale: float | None = None, mf: int = 0, nf: int = 0) -> torch.Tensor:
+    """Query-batch 1x1 conv (conv1x1_small.hip), stride 1 or 2, no padding, on
+    NHWC [B,H,W,Cin] bf16 or e4m3; w: row-major [N, Cin] of x's type (e4m3: with
+    ``alpha`` [N] = s_x * s_w[n]). Cin in {64, 128, .., 2048} (bf16) or {128,
+    256, .., 2048} (e4m3), N % 16 == 0. ``out_scale`` given means e4m3 output
+    (value / out_scale, saturating), else bf16; ``res`` (the output's shape and
+    type; e4m3: times res_scale) is added before the ReLU. mf, nf: 16-pixel x
+    16-channel fragments per workgroup (0: conv1x1_small_pick)."""
+    _need_cuda(x, w, bias, alpha, res)
+    C = native()
+    in8, out8 = x.dtype in (FP8, torch.uint8), out_scale is not None
+    if x.dim() != 4 or w.dim() != 2 or (not in8 and x.dtype != torch.bfloat16) or (w.dtype in (FP8, torch.uint8)) != in8 \
+            or (not in8 and w.dtype != torch.bfloat16):
+        raise ValueError("conv1x1_small: x is bf16 or e4m3 NHWC, w [N, Cin] of the same type")
+    B, H, W, Cin = x.shape
+    N = w.shape[0]
+    if w.shape[1] != Cin or not C.conv1x1_small_supported(B, H, W, Cin, N, stride, in8, out8):
+        raise ValueError("conv1x1_small: unsupported shape")
+    if in8 and alpha is None:
+        raise ValueError("conv1x1_small: e4m3 input needs alpha")
+    if bool(mf) != bool(nf):
+        raise ValueError("conv1x1_small: give both mf and nf, or neither")
+    if not mf:
+        cus = torch.cuda.get_device_properties(x.device).multi_processor_count
+        mf, nf = C.conv1x1_small_pick(B, H, W, Cin, N, stride, in8, out8, cus)
+    Ho, Wo = C.conv_out_dim(H, 1, stride, 0), C.conv_out_dim(W, 1, stride, 0)
+    y = torch.empty(B, Ho, Wo, N, dtype=FP8 if out8 else torch.bfloat16, device=x.device)
+    extra = {}
+    if res is not None:
+        if tuple(res.shape) != tuple(y.shape) or (res.dtype in (FP8, torch.uint8)) != out8 \
+                or (not out8 and res.dtype != torch.bfloat16):
+            raise ValueError("conv1x1_small: res has the output's shape and type")
+        extra.update(res=_ptr(res.contiguous()), res_scale=float(res_scale))
+    if in8:
+        extra.update(alpha=_ptr(_f32(alpha, N, "alpha")))
+    if out8:
+        extra.update(out_inv_scale=1.0 / float(out_scale))
+    C.conv1x1_small(_ptr(x.contiguous()), _ptr(w.contiguous()), _ptr(_f32(bias, N, "bias")), _ptr(y), B, H, W, Cin, N,
+                    stride, relu, in8, out8, int(mf), int(nf), _stream(), **extra)
+    return y
+
+
 def maxpool2d(x: torch.Tensor, k: int = 3, stride: int = 2, pad: int = 1) -> torch.Tensor:
     _need_cuda(x)
     C = native()

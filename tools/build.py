@@ -120,6 +120,7 @@ HIPCC_FILE_FLAGS = {
     "fc8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "conv_small8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "conv_smallk.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "conv1x1_small.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 
